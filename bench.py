@@ -24,18 +24,26 @@ broadcast and the timed steps exchange their gradients between the step's two gr
 `python bench.py --gpus N` without WORLD_SIZE in the environment launches its own N ranks (one child process per
 GPU, started before this process makes any GPU call; rank 0's line is passed through, a failing rank fails the run).
 
+A plain run sets up, warms up, times the --steps steps, writes what the last timed step computed when --dump-outputs DIR
+is given (DIR/<name>.npy, float32 / float64, at most 64 MB: the losses, the pre-clip gradient norm and the student's
+updated parameters and BatchNorm buffers), and prints the line.  Everything else it measures runs only with --full:
+the CPU baseline, the `secondary` child runs, the eagerly launched HIP-event steps behind `eager_launch_events`
+(and --layer-table), the host-issue probe and, for --workload dense16d, the blurs after the first.
+The inputs are seeded (batches, weights, torch.manual_seed(0) for the OT loss's sampling keys): the same arguments
+give the same inputs, and on one build the same outputs, run after run.
+
 The single JSON line carries, besides the contract fields:
   roofline     -- dominant kernel family = the implicit-GEMM convolutions (kd6d_conv2d_{fwd,dgrad,wgrad} and the
                   grouped weight gradient): `achieved` = algorithmic conv FLOP of a step (SURVEY.md 8(d), 2*MAC on the
                   reference's channel counts) / WALL ms_per_step of the timed, hipGraph-replayed steps, per GPU;
-                  peak = 2.5 PFLOP/s dense bf16 MFMA.  `eager_launch_events` keeps the per-launch HIP-event figures of
+                  peak = 2.5 PFLOP/s dense bf16 MFMA.  `eager_launch_events` (--full) keeps the per-launch HIP-event figures of
                   a few eagerly launched single-stream steps after the timed region (a different schedule: per-family
                   kernel efficiency, not step time).  `traffic` = HBM bytes of the conv family per step from the
                   rocprofv3 PMC passes committed under profiles/ (tools/pmc_traffic.sh), null when that file does not
                   describe the configuration being run.
-  cpu_baseline -- oracle/kd_step_ref.py (pure-torch fp32 port of the reference step, validated
+  cpu_baseline -- (--full) oracle/kd_step_ref.py (pure-torch fp32 port of the reference step, validated
                   against the imported reference) timed on this host's cores, rank 0, N=1 only.
-  secondary    -- (N=1, default workload only) 20-step timings of the other BASELINE configurations, each run by this
+  secondary    -- (--full, N=1, default workload only) 20-step timings of the other BASELINE configurations, each run by this
                   same script in a child process AFTER the headline's timed region: config 4's per-GPU shard
                   (--workload linemod13), full 480x640 frames (--frame full640), one teacher forward per step
                   (--teacher-group 1), strictly sequential steps (--no-pipeline), the one-rank rehearsal of the data-parallel
@@ -92,6 +100,13 @@ def parse():
                    help="A/B aid: the student's in-stage BatchNorm + LeakyReLU applied by the next block's convolution while it "
                         "loads (kd6d_conv2d_fwd_block): 0 never, 1 where the next block is a 1x1 convolution, 2 every in-stage "
                         "transition; default = the engine's measured choice")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: the CPU baseline, the `secondary` child runs, the eagerly "
+                        "launched HIP-event steps (roofline.eager_launch_events, --layer-table), the host-issue probe and the "
+                        "dense16d workload's other blurs")
+    p.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                   help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64, "
+                        "at most 64 MB in all)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-secondary", action="store_true", help="skip the `secondary` timings (child runs of the other configs)")
     p.add_argument("--no-launch-events", action="store_true",
@@ -114,11 +129,17 @@ def parse():
     p.add_argument("--no-pipeline", action="store_true",
                    help="do not overlap the teacher forward of batch k+1 with the student step of batch k")
     p.add_argument("--cpu-steps", type=int, default=4)
-    p.add_argument("--layer-table", type=str, default="", help="write the per-launch conv table (instrumented steps) here")
+    p.add_argument("--layer-table", type=str, default="",
+                   help="with --full: write the per-launch conv table (instrumented steps) here")
     p.add_argument("--timeline", action="store_true",
                    help="analysis aid: capture device timestamp markers into the graph and print the phase boundaries of the "
                         "last replayed step to stderr (adds ~15 one-thread launches per step)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.layer_table and (not args.full or args.no_launch_events):
+        p.error("--layer-table needs the instrumented steps of --full")
+    return args
 
 
 WORKLOAD_YAML = {"ape": "ape.yaml", "linemod13": "linemod13.yaml", "dense16d": "dense16d.yaml"}
@@ -261,6 +282,9 @@ def main():
         if n_vis < world_env:
             raise SystemExit("bench.py: %d GPUs needed, %d visible (rank %s)" % (world_env, n_vis, os.environ.get("RANK", "0")))
     pinned = pin_host_thread(int(os.environ.get("LOCAL_RANK", 0)), world_env)
+    # the same inputs every run, as train_kd.py seeds it: the OT loss's device-side sampling keys derive from this seed
+    # (kd6d/kd_losses.py), everything else is seeded explicitly
+    torch.manual_seed(0)
     out_fd = _StdoutToStderr()
     if args.workload == "dense16d":
         return bench_dense(args, out_fd)
@@ -431,6 +455,15 @@ def main():
         elapsed = max(float(x.item()) for x in every)          # the contract's MAX over ranks
     losses = {k: float(v) for k, v in ld.items()}
     finite = all(v == v and abs(v) != float("inf") for v in losses.values())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the loss scalars and the pre-clip gradient norm, and what it left
+        # in the student -- the updated parameters (the trained region of the flat fp32 store) and BatchNorm buffers
+        st = student.net.store
+        arrays = {k: [v] for k, v in losses.items()}
+        arrays["grad_norm"] = [float(opt.grad_norm())]
+        arrays["student_params"] = st.params[:st.n_train].float().cpu().numpy()
+        arrays["student_buffers"] = st.bufs.float().cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     # the one-launch BN / GN backward kernels wait at in-kernel barriers with a bounded spin: a wait that gave up
     # means wrong gradients in the timed steps, so the run is invalid (reported in the JSON line, non-zero exit)
     barrier_timeouts = int(ops.lib.kd6d_barrier_timeouts())
@@ -440,9 +473,9 @@ def main():
         t0 = t[slots["step.start"]]
         for name, idx in sorted(slots.items(), key=lambda kv: t[kv[1]]):
             print("timeline %-28s %9.1f us" % (name, (t[idx] - t0) * 0.01), file=sys.stderr)
-    # host cost of issuing one step onto an idle GPU (in the timed loop the host mostly waits for queue space)
+    # (--full) host cost of issuing one step onto an idle GPU (in the timed loop the host mostly waits for queue space)
     t_issue = []
-    for j in range(3):
+    for j in range(3 if args.full else 0):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         step(args.warmup + args.steps + j)
@@ -451,15 +484,15 @@ def main():
 
     # ---- roofline leg: per-launch HIP-event timing of every conv launch, in instrumented steps that
     # every rank runs (the step contains the gradient all-reduce) but only rank 0 records ----
-    n_instr = 0 if args.no_launch_events else 3
-    if rank == 0:
+    n_instr = 3 if (args.full and not args.no_launch_events) else 0
+    if rank == 0 and n_instr:
         ops.profile_begin()
     for i in range(n_instr):
         # eager launches cost the host ~15 us each, more than most of these kernels run: park the GPU behind a spin
         # kernel while the host queues the step, so that the event pairs bracket back-to-back kernels, not launch gaps
         torch.cuda._sleep(int(2.0e9 * 0.010))
         step(args.warmup + args.steps + i, eager=True)
-    rec = ops.profile_end() if rank == 0 else []
+    rec = ops.profile_end() if (rank == 0 and n_instr) else []
 
     out = None
     if rank == 0 and args.layer_table and n_instr:
@@ -535,16 +568,17 @@ def main():
                           "weights": "random-init (seeded), teacher cls bias set so ~10 cells/img pass 0.1"},
                "losses_last_step": losses, "finite": finite and not args.debug_skip_teacher, "barrier_timeouts": barrier_timeouts,
                "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3,
-               "host_issue_ms_idle_gpu": min(t_issue) * 1e3,
                "roofline": roof}
+        if t_issue:
+            out["host_issue_ms_idle_gpu"] = min(t_issue) * 1e3
         # ---- CPU baseline leg (oracle = port of the reference step), rank 0, N=1 only ----
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, B, full)
         if pinned:
             out["config"]["host_cpus_per_rank"] = pinned
         default_run = (args.workload == "ape" and not full and not args.no_pipeline and not args.no_graph and args.teacher_group == 3
                        and args.student == "darknet_tiny_h" and args.precision == "bf16" and not args.opt and not args.tune)
-        if world == 1 and default_run and not args.no_secondary:
+        if world == 1 and default_run and args.full and not args.no_secondary:
             out["secondary"] = secondary_runs(args)
     if use_pg:
         dist.barrier()
@@ -584,15 +618,16 @@ def bench_dense(args, out_fd):
     mk = lambda *shape: torch.from_numpy(sig(r.normal(0, 2, shape)).astype(np.float32)).to(dev)     # noqa: E731
     x, y, a, b = mk(N, D), mk(M, D), mk(N), mk(M)
     results = []
-    steps = max(1, min(args.steps, 20))
-    for blur in kd["BLUR"]:
+    steps, warmup = args.steps, max(args.warmup, 0)
+    # the headline is the first blur; the others are further configurations (--full)
+    for blur in (kd["BLUR"] if args.full else kd["BLUR"][:1]):
         diam = float(torch.sqrt(((torch.maximum(x.max(0).values, y.max(0).values)
                                   - torch.minimum(x.min(0).values, y.min(0).values)) ** 2).sum()))
         n_eps = 2 + int(np.ceil((2 * np.log(blur) - 2 * np.log(diam)) / (2 * np.log(kd["SCALING"]))))
         passes = 4 * (1 + n_eps + 1)
         run = lambda: ops.sinkhorn_dense(x, a, y, b, blur=blur, scaling=kd["SCALING"], reach=kd["REACH"],   # noqa: E731
                                          diameter=diam, p=kd["P"])
-        for _ in range(max(1, min(args.warmup, 3))):
+        for _ in range(warmup):
             run()
         if world > 1:
             dist.barrier()
@@ -609,6 +644,10 @@ def bench_dense(args, out_fd):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         ms = el / steps * 1e3
+        if args.dump_outputs and rank == 0 and not results:
+            # what the headline's last timed call returned: the divergence and its gradients in x and in alpha
+            dump_outputs(args.dump_outputs, {"loss": loss.detach().double().cpu().numpy().reshape(-1),
+                                             "grad_x": gx.float().cpu().numpy(), "grad_alpha": ga.float().cpu().numpy()})
         pairs = passes * float(N) * float(M)
         # which passes run where (csrc/sinkhorn_dense.hip): with D = 16 the gradient-free softmin passes go to the matrix
         # pipe (inner products as six bf16 MFMAs on three-way split operands: 6 x 2 x 16 FLOP per pair) while
@@ -648,7 +687,7 @@ def bench_dense(args, out_fd):
     head = results[0]
     out_fd.emit(json.dumps({
         "metric": "dense-OT KD loss images/sec (Sinkhorn divergence value + gradients, one 128x128x16-D problem per image)",
-        "value": head["images_per_s"], "unit": "images/s", "n_gpus": world, "steps": steps, "warmup": min(args.warmup, 3),
+        "value": head["images_per_s"], "unit": "images/s", "n_gpus": world, "steps": steps, "warmup": warmup,
         "ms_per_step": head["ms_per_image"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": "BASELINE config 5 (configs/dense16d.yaml): N = M = %d cells, D = %d, p=2, blur %s, scaling %s, "
@@ -696,7 +735,7 @@ def secondary_runs(args):
     res = []
     for name, what, flags in SECONDARY:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batch",
-               str(args.batch), "--no-cpu-baseline", "--no-secondary", "--no-launch-events"] + flags
+               str(args.batch), "--full", "--no-cpu-baseline", "--no-secondary", "--no-launch-events"] + flags
         entry = {"name": name, "what": what, "flags": " ".join(flags)}
         t0 = time.perf_counter()
         env = None
@@ -724,6 +763,31 @@ def secondary_runs(args):
         entry["wall_s"] = time.perf_counter() - t0
         res.append(entry)
     return res
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 for scalars and float64 arrays, float32 otherwise.  Should
+    the arrays exceed MAX_DUMP_BYTES together, the largest ones are cut to a fixed, seeded sample of their elements."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 or a.size == 1 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    for name in sorted(out, key=lambda n: -out[n].nbytes):
+        if total <= MAX_DUMP_BYTES:
+            break
+        a = out[name].reshape(-1)
+        keep = max(1, a.size - (total - MAX_DUMP_BYTES + a.itemsize - 1) // a.itemsize)
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+        total -= a.nbytes - keep * a.itemsize
+        out[name] = a[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def write_layer_table(path, rec, n_instr):

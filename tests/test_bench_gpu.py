@@ -42,6 +42,38 @@ def test_bench_line_contract_default_launch_mode(gpu_device):
     assert cfg["teacher_segments_in_timed_region"] == 7 and cfg["teacher_images_in_timed_region"] == 7 * 16
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(gpu_device, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the --full legs (CPU baseline, secondary
+    child runs, eager HIP-event steps, host-issue probe); --dump-outputs DIR writes what the last timed step computed --
+    its losses, which the line reports too, the gradient norm and the student's updated weights -- as float32 / float64
+    .npy files, 64 MB at most.  The inputs are seeded, so a second run with the same arguments dumps the same arrays."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = _run("--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["finite"] is True
+    assert d["value"] == pytest.approx(16 * 1e3 / d["ms_per_step"], rel=1e-6)
+    for k in ("cpu_baseline", "secondary", "host_issue_ms_idle_gpu"):
+        assert k not in d, k
+    assert "eager_launch_events" not in d["roofline"]
+    files = sorted(out.glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    got = {f.stem: np.load(f) for f in files}
+    assert {"loss_cls", "loss_reg", "loss_kd", "grad_norm", "student_params", "student_buffers"} <= set(got), sorted(got)
+    for name, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), name
+    for k, v in d["losses_last_step"].items():
+        assert float(got[k][0]) == v, (k, got[k], v)
+    again = tmp_path / "again"
+    r = _run("--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(again))
+    assert r.returncode == 0, r.stderr[-2000:]
+    for name, a in got.items():
+        assert np.array_equal(np.load(again / (name + ".npy")), a), name
+
+
 def test_bench_self_launch_reports_missing_gpus(gpu_device):
     """`python bench.py --gpus N` with no launcher around it starts its own N ranks before touching the GPU; with fewer
     GPUs than ranks the children say so and the run fails -- no usage message, no hang."""

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-pmc_dense}
 mkdir -p $OUT
 for pass in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_LDS SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU SQ_WAVES" "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum"; do
   tag=$(echo $pass | cut -d' ' -f1)
-  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $OUT/$tag -o p -- python3 $R/bench.py --workload dense16d --steps 2 --warmup 1 > $OUT/log_$tag.txt 2>&1
+  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $OUT/$tag -o p -- python3 $R/bench.py --full --workload dense16d --steps 2 --warmup 1 > $OUT/log_$tag.txt 2>&1
 done
 python3 - <<PY > $OUT/summary.txt
 import csv, glob, collections

@@ -11,6 +11,6 @@ OUT=$R/gpurun_out/pmc_traffic
 mkdir -p $OUT
 if [ "$1" = "graph" ]; then ARGS="--steps 30 --warmup 3"; else ARGS="--steps 2 --warmup 1 --no-graph"; fi
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o p -- python3 $R/bench.py $ARGS --no-cpu-baseline --no-secondary --no-launch-events > $OUT/log_$c.txt 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o p -- python3 $R/bench.py --full $ARGS --no-cpu-baseline --no-secondary --no-launch-events > $OUT/log_$c.txt 2>&1
 done
 python3 $R/tools/pmc_traffic_post.py $OUT
