@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define KD6D_ABI_VERSION 8
+#define KD6D_ABI_VERSION 9
 
 enum { KD6D_BF16 = 0, KD6D_F32 = 1 };
 enum { KD6D_ACT_NONE = 0, KD6D_ACT_LEAKY = 1, KD6D_ACT_RELU = 2 };
@@ -347,6 +347,13 @@ int kd6d_bn_train_fwd(int dtype, int x_f32, const void* x, void* y, int64_t rows
                       const kd6d_acc* sumsq, const float* gamma, const float* beta, float eps, float momentum,
                       float* running_mean, float* running_var, float* save_mean, float* save_invstd,
                       int act, void* stream);
+/* kd6d_bn_train_fwd plus a residual added after the activation: y = act(bn(x)) + residual, summed in fp32 and rounded
+ * once to `dtype` (the DarkUnit of backbone/darknet53.py:54-58 in training mode).  residual has y's dtype and layout
+ * (rows, C); statistics, running buffers and save_mean / save_invstd as in kd6d_bn_train_fwd. */
+int kd6d_bn_train_fwd_res(int dtype, int x_f32, const void* x, const void* residual, void* y, int64_t rows, int C,
+                          const kd6d_acc* sum, const kd6d_acc* sumsq, const float* gamma, const float* beta, float eps,
+                          float momentum, float* running_mean, float* running_var, float* save_mean,
+                          float* save_invstd, int act, void* stream);
 int kd6d_bn_train_bwd_reduce(int dtype, int x_f32, const void* x, const void* dz, int64_t rows, int C,
                              const float* mean, const float* invstd, const float* gamma, const float* beta,
                              int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat, int replicas, void* stream);

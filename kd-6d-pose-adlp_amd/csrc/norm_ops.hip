@@ -232,13 +232,16 @@ __device__ __forceinline__ void bn_fwd_scale_shift(
   }
 }
 
-// y = act(gamma * (x - mean) * invstd + beta), mean/var from the batch sums.
-template <typename T, typename TX>
+// y = act(gamma * (x - mean) * invstd + beta) [+ res], mean/var from the batch sums.
+// RES: the DarkUnit's identity (backbone/darknet53.py:54-58) added after the activation in fp32, one rounding to T;
+// res has y's dtype and layout.  RES = false is the plain kernel (res unused).
+template <typename T, typename TX, bool RES = false>
 __global__ __launch_bounds__(kThreads) void bn_apply_fwd_kernel(
     const TX* __restrict__ x, T* __restrict__ y, long long ngran, int C, float inv_rows,
     const acc_t* __restrict__ sum, const acc_t* __restrict__ sumsq, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, float momentum, float unbias,
-    float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act) {
+    float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act,
+    const T* __restrict__ res = nullptr) {
   constexpr int EG = Granule<T>::N;
   const int cgs = C / EG;
   const int cg = threadIdx.x % cgs;
@@ -254,6 +257,12 @@ __global__ __launch_bounds__(kThreads) void bn_apply_fwd_kernel(
     load_x<TX, EG>(x, g, v);
 #pragma unroll
     for (int e = 0; e < EG; ++e) v[e] = bn_act(v[e], sc[e], sh[e], act);
+    if constexpr (RES) {
+      float r[EG];
+      granule_to_f32<T>(reinterpret_cast<const u32x4_t*>(res)[g], r);
+#pragma unroll
+      for (int e = 0; e < EG; ++e) v[e] += r[e];
+    }
     yg[g] = f32_to_granule<T>(v);
   }
 }
@@ -1601,6 +1610,31 @@ extern "C" int kd6d_bn_train_fwd(int dtype, int x_f32, const void* x, void* y, i
                                    (const TX_*)x, (T_*)y, ngran, C, inv_rows, sum, sumsq, gamma, beta, eps,
                                    momentum, unbias, running_mean, running_var, save_mean, save_invstd, act));
   KD6D_CHECK_LAUNCH("kd6d_bn_train_fwd");
+  return KD6D_OK;
+}
+
+extern "C" int kd6d_bn_train_fwd_res(int dtype, int x_f32, const void* x, const void* residual, void* y, int64_t rows,
+                                     int C, const kd6d_acc* sum_acc, const kd6d_acc* sumsq_acc, const float* gamma,
+                                     const float* beta, float eps, float momentum, float* running_mean,
+                                     float* running_var, float* save_mean, float* save_invstd, int act, void* stream) {
+  int rc = check_channels(dtype, C, "kd6d_bn_train_fwd_res");
+  if (rc) return rc;
+  const acc_t* sum = reinterpret_cast<const acc_t*>(sum_acc);
+  const acc_t* sumsq = reinterpret_cast<const acc_t*>(sumsq_acc);
+  KD6D_CHECK_ARG(x && y && sum && sumsq && gamma && beta && rows > 0, "kd6d_bn_train_fwd_res: bad arguments");
+  KD6D_CHECK_ARG(residual, "kd6d_bn_train_fwd_res: null residual");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int eg = dtype == KD6D_BF16 ? 8 : 4;
+  const long long ngran = rows * (C / eg);
+  const float inv_rows = 1.f / (float)rows;
+  const float unbias = rows > 1 ? (float)rows / (float)(rows - 1) : 1.f;
+  const int nb = grid_for((ngran + 3) / 4);
+  DISPATCH_TTX(dtype, x_f32,
+               hipLaunchKernelGGL((bn_apply_fwd_kernel<T_, TX_, true>), dim3(nb), dim3(kThreads), 0, st,
+                                   (const TX_*)x, (T_*)y, ngran, C, inv_rows, sum, sumsq, gamma, beta, eps,
+                                   momentum, unbias, running_mean, running_var, save_mean, save_invstd, act,
+                                   (const T_*)residual));
+  KD6D_CHECK_LAUNCH("kd6d_bn_train_fwd_res");
   return KD6D_OK;
 }
 

@@ -15,7 +15,7 @@ KD6D_F32 = 1
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 GN_STATS_READY, GN_WS_ZEROED = 1, 2
 MAX_SEG = 5
-ABI_VERSION = 8
+ABI_VERSION = 9
 ACC_ACT, ACC_GRAD = 32, 52           # KD6D_ACC_ACT / KD6D_ACC_GRAD: fixed-point classes of kd6d_acc
 NORM_GROUP, NORM_BATCH = 1, 2
 BN_FUSED_REPLICAS = 8
@@ -117,6 +117,7 @@ SIGNATURES = {
     "kd6d_pack_dgrad_weights": [_I, _P, _P, _P, _I, _I, _P],
     "kd6d_colstats": [_I, _P, _I64, _I, _P, _P, _P],
     "kd6d_bn_train_fwd": [_I, _I, _P, _P, _I64, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P],
+    "kd6d_bn_train_fwd_res": [_I, _I, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P],
     "kd6d_bn_train_bwd_reduce": [_I, _I, _P, _P, _I64, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P],
     "kd6d_bn_train_bwd_apply": [_I, _I, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     "kd6d_barrier_timeouts": [],

@@ -368,8 +368,10 @@ class ConvBlock:
         y, g = self.conv.fwd(x, batch, levels, scale=sc, shift=sh, act=ACT_LEAKY, residual=residual)
         return y, g.levels_out
 
-    def fwd_train(self, x, batch, levels, tape, pool=False, pending=None, defer=False):
-        """pool=True: the block is followed by MaxPool2d(2,2) (darknet.py:94-97); normalisation, activation and
+    def fwd_train(self, x, batch, levels, tape, pool=False, pending=None, defer=False, residual=None):
+        """residual: a tensor of the output's shape and dtype added after the activation (the DarkUnit's identity,
+        backbone/darknet53.py:54-58; kd6d_bn_train_fwd_res); only on the plain path (no pooling, deferral or fusion).
+        pool=True: the block is followed by MaxPool2d(2,2) (darknet.py:94-97); normalisation, activation and
         pooling run as one kernel and only the pooled tensor is stored (csrc/norm_ops.hip, bn_pool_*).
         defer=True: this block's BatchNorm + LeakyReLU is NOT launched here -- the next block of the stage applies it
         while it loads its input (kd6d_conv2d_fwd_block); returns (None, levels, pending record for that block).
@@ -382,6 +384,9 @@ class ConvBlock:
         s = net.scratch(self.name, self.scratch_floats(geom.rows_out))
         ssum, ssq = s[0:A * c], s[A * c:2 * A * c]
         mean, invstd = s[2 * A * c:(2 * A + 1) * c], s[(2 * A + 1) * c:(2 * A + 2) * c]
+        if residual is not None:
+            assert not pool and pending is None and not defer and not net.fuse_norm_on(), \
+                "ConvBlock.fwd_train: the residual add runs only on the separate normalise launch"
         if pending is not None or defer:
             raw = net.buf(self.name + ".raw", (geom.rows_out, c), torch.float32)
             bn_in = z_in = None
@@ -434,8 +439,12 @@ class ConvBlock:
             tape.append((self, x, raw, batch, tuple(levels), (h, w)))
             return z, [(h // 2, w // 2)], None
         z = net.buf(self.name + ".z", raw.shape, net.dtype)
-        ops.bn_train_fwd(raw, z, ssum, ssq, st.storage(self.bn.gamma), st.storage(self.bn.beta), 1e-5, 0.1,
-                         st.storage(self.bn.rm), st.storage(self.bn.rv), mean, invstd, ACT_LEAKY)
+        if residual is not None:
+            ops.bn_train_fwd_res(raw, residual, z, ssum, ssq, st.storage(self.bn.gamma), st.storage(self.bn.beta), 1e-5,
+                                 0.1, st.storage(self.bn.rm), st.storage(self.bn.rv), mean, invstd, ACT_LEAKY)
+        else:
+            ops.bn_train_fwd(raw, z, ssum, ssq, st.storage(self.bn.gamma), st.storage(self.bn.beta), 1e-5, 0.1,
+                             st.storage(self.bn.rm), st.storage(self.bn.rv), mean, invstd, ACT_LEAKY)
         tape.append((self, x, raw, batch, tuple(levels), None))
         return z, g.levels_out, None
 
@@ -775,22 +784,57 @@ class PoseNet:
             self.cut_hook()
 
     def _backbone53(self, x, B, lv):
-        x, lv = self.init_block.fwd_eval(x, B, lv) if not self.training else self.init_block.fwd_train(x, B, lv, self.tape)[:2]
+        if self.training:
+            # training (the teacher recipe): every block is conv (+ fused statistics) -> normalise launch; the
+            # transform-on-load and conv + normalisation fusions have no residual path
+            assert not self.fuse_norm_on() and not self.bn_on_load, \
+                "darknet53 training runs without fuse_norm and bn_on_load"
+            tape = self.tape
+            x, lv = self.init_block.fwd_train(x, B, lv, tape)[:2]
+            feats = []
+            for i, units in enumerate(self.stages):
+                for u in units:
+                    if u[0] == "down":
+                        x, lv = u[1].fwd_train(x, B, lv, tape)[:2]
+                    else:
+                        x, lv = self.unit_fwd_train(u, x, B, lv)
+                tape.append(("stage", i))
+                feats.append((x, lv))
+            return feats
+        x, lv = self.init_block.fwd_eval(x, B, lv)
         self._cut()
         feats = []
         for units in self.stages:
             for u in units:
                 if u[0] == "down":
-                    x, lv = u[1].fwd_eval(x, B, lv) if not self.training else u[1].fwd_train(x, B, lv, self.tape)[:2]
+                    x, lv = u[1].fwd_eval(x, B, lv)
                 else:
-                    if self.training:
-                        raise NotImplementedError("darknet53 is only run as the frozen teacher (eval mode) "
-                                                  "in the KD step; training it is outside the hot path")
                     h, _ = u[1].fwd_eval(x, B, lv)
                     x, lv = u[2].fwd_eval(h, B, lv, residual=x)
                 self._cut()
             feats.append((x, lv))
         return feats
+
+    def unit_fwd_train(self, u, x, B, lv):
+        """DarkUnit ("res", conv1 block, conv2 block) in training mode: conv2(conv1(x)) + x with the add behind conv2's
+        LeakyReLU (backbone/darknet53.py:54-58); one ("unit", rec1, rec2) entry on the tape."""
+        tape = self.tape
+        n0 = len(tape)
+        h, _ = u[1].fwd_train(x, B, lv, tape)[:2]
+        y, lv = u[2].fwd_train(h, B, lv, tape, residual=x)[:2]
+        rec1, rec2 = tape[n0:]
+        tape[n0:] = [("unit", rec1, rec2)]
+        return y, lv
+
+    def unit_bwd(self, rec, grad):
+        """Backward of a ("unit", rec1, rec2) tape entry: grad (the gradient of the unit's output) becomes, in place, the
+        gradient of its input, d_out + conv1's data gradient."""
+        _, rec1, rec2 = rec
+        d_mid = rec2[0].bwd(rec2, grad, dx=self.buf(rec2[0].name + ".dx", rec2[1].shape))
+        # written over d_out: on this stream conv2's BatchNorm backward has already consumed d_out, and the forked
+        # weight gradients read only x and draw
+        rec1[0].bwd(rec1, d_mid, dx=grad, accumulate=True)
+        return grad
 
     def _backbone_tiny(self, x, B, lv):
         feats = []
@@ -952,7 +996,7 @@ class PoseNet:
     def backward(self, dcls, dreg):
         """dcls (rows,16), dreg (rows,240) in self.dtype: gradients w.r.t. the UNSCALED head outputs
         (the Scale module's factor is already folded into dreg by kd6d_loss_backward)."""
-        assert self.training and self.arch != "darknet53"
+        assert self.training
         B, lv_all, r, oc = self.batch, self.levels, self.rows, self.out_channel
         if self.use_wgrad_group and self.dtype == torch.bfloat16 and self.wgrad_group is None:
             self.wgrad_group = ops.WgradGroup(self.wgrad_group_wgs or max(ops.device_cu_count() // 2, 1))
@@ -1059,10 +1103,47 @@ class PoseNet:
             # every gradient outside the backbone has been issued (on this stream or on the weight-gradient streams):
             # a data-parallel caller starts their exchange here, beside the backbone sweep
             self.grad_hook()
-        # ---- backbone (tiny): walk the tape in reverse ----
-        # feats index -> gradient arriving from the FPN; out4 = index 3 (after stage 5), out3 = index 2
-        grad = dfeat[top]
-        pending = {2: dfeat.get(2)}            # added when the sweep reaches out3 (after pool3)
+        if self.arch == "darknet53":
+            self._backbone53_bwd(dfeat)
+        else:
+            self._backbone_tiny_bwd(dfeat[top], dfeat.get(2))
+        ops.mark("student.bwd.main.end")
+        for side in (self.side_streams or ([self.side_stream] if self.side_stream is not None else [])):
+            torch.cuda.current_stream().wait_stream(side)
+        # every accumulated gradient (per-layer weight / bias gradients, GroupNorm gains and shifts, the head's scales)
+        # -> fp32, accumulators cleared for the next step: one launch.  A caller that resolved the FPN + head part
+        # early (grad_hook, the overlapped exchange) sets resolve_hi to where that part begins.
+        self.store.resolve_grads(0, self.resolve_hi)
+        return None
+
+    def _backbone53_bwd(self, dfeat):
+        """Reverse sweep of Darknet-53's backbone over the training tape.  dfeat: stage index (2, 3, 4) -> the FPN's
+        gradient of that stage's output; the stage-3 / stage-4 ones are added by the data gradient of the next stage's
+        down-sampling block (accumulate=True into the FPN's buffer)."""
+        tape = self.tape
+        grad = dfeat[len(self.stages) - 1]
+        for i_rec in range(len(tape) - 1, -1, -1):
+            rec = tape[i_rec]
+            if rec[0] == "stage":
+                continue
+            if rec[0] == "unit":
+                grad = self.unit_bwd(rec, grad)
+                continue
+            blk = rec[0]
+            if i_rec == 0:                      # the init block: no gradient of the image
+                blk.bwd(rec, grad, need_dx=False)
+                continue
+            prev = tape[i_rec - 1]
+            if prev[0] == "stage" and prev[1] in dfeat:
+                # the first block of the stage after a feature the FPN reads: its data gradient adds into the FPN's
+                grad = blk.bwd(rec, grad, dx=dfeat[prev[1]], accumulate=True)
+            else:
+                grad = blk.bwd(rec, grad, dx=self.buf(blk.name + ".dx", rec[1].shape))
+
+    def _backbone_tiny_bwd(self, grad, dfeat2):
+        """Reverse sweep of a darknet-tiny backbone over the training tape.  grad: the FPN's gradient of out4 (after
+        stage 5); dfeat2: of out3 (after stage 3), added when the sweep reaches it."""
+        pending = {2: dfeat2}                  # added when the sweep reaches out3 (after pool3)
         stage_of_pool = {}
         i_rec = len(self.tape) - 1
         pools_seen = 0
@@ -1086,11 +1167,3 @@ class PoseNet:
                 grad = blk.bwd(rec, grad, need_dx=need_dx,
                                dx=self.buf(blk.name + ".dx", rec[1].shape) if need_dx else None)
             i_rec -= 1
-        ops.mark("student.bwd.main.end")
-        for side in (self.side_streams or ([self.side_stream] if self.side_stream is not None else [])):
-            torch.cuda.current_stream().wait_stream(side)
-        # every accumulated gradient (per-layer weight / bias gradients, GroupNorm gains and shifts, the head's scales)
-        # -> fp32, accumulators cleared for the next step: one launch.  A caller that resolved the FPN + head part
-        # early (grad_hook, the overlapped exchange) sets resolve_hi to where that part begins.
-        self.store.resolve_grads(0, self.resolve_hi)
-        return None

@@ -398,6 +398,19 @@ def bn_train_fwd(x, y, sum_, sumsq, gamma, beta, eps, momentum, running_mean, ru
     return y
 
 
+def bn_train_fwd_res(x, residual, y, sum_, sumsq, gamma, beta, eps, momentum, running_mean, running_var,
+                     save_mean, save_invstd, act):
+    """bn_train_fwd with the DarkUnit's identity: y = act(bn(x)) + residual (residual: y's dtype and shape)."""
+    rows, c = x.shape
+    assert residual.shape == y.shape and residual.dtype == y.dtype
+    check(lib.kd6d_bn_train_fwd_res(dt_code(y.dtype), _xf32(x, y.dtype), _ptr(x), _ptr(residual), _ptr(y), rows, c,
+                                    _ptr(sum_), _ptr(sumsq), _ptr(gamma), _ptr(beta), eps, momentum,
+                                    _ptr(running_mean), _ptr(running_var), _ptr(save_mean), _ptr(save_invstd), act,
+                                    _stream()),
+          "kd6d_bn_train_fwd_res")
+    return y
+
+
 BARRIER_WORDS = 32          # KD6D_BARRIER_WORDS: pre-zeroed 32-bit words of an in-kernel barrier (kd6d.h)
 
 
