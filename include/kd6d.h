@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define KD6D_ABI_VERSION 9
+#define KD6D_ABI_VERSION 10
 
 enum { KD6D_BF16 = 0, KD6D_F32 = 1 };
 enum { KD6D_ACT_NONE = 0, KD6D_ACT_LEAKY = 1, KD6D_ACT_RELU = 2 };
@@ -539,6 +539,35 @@ int kd6d_sinkhorn_dense_fwd_bwd(const float* x, const float* alpha, const float*
 int kd6d_dzi_crop(const uint8_t* frames_bgr, const float* masks, int B, int H, int W, const float* center_scale,
                   const float* lut_rgb, int out_res, float* images_nchw, float* masks_out, float* bbox_trans,
                   float* bbox_scale, void* stream);
+
+/* ---- train-time augmentation of full frames (csrc/augment.hip): the reference's train transform chain
+ * (libs/train_libs.py:212-238: Resize, RandomOcclusion, RandomShiftScaleRotate, RandomHSV, RandomSmooth,
+ * RandomNoise, Grayscalize) and remove_invalids (poses.py:172-200), on the uint8 BGR frames (B,H,W,3) and float
+ * instance masks (B,H,W) the DZI crop consumes.  The host (kd6d/libs/augment.py) draws every scalar parameter;
+ * per-pixel randomness is a counter-based hash of (key, image, pixel, channel).  The arithmetic restates cv2's
+ * 8-bit fixed-point paths (parity unpinned at the cv2 boundary; tests/augment_ref.py).
+ * kd6d_aug_warp_u8     fwd_mats (B,6) double: FORWARD 2x3 matrices (dst = M src), inverted in double like
+ *                      cv2.warpAffine; frame bilinear with 15-bit tap weights and border 128, mask nearest with
+ *                      border 0.  src_mask / dst_mask both or neither; src != dst.
+ * kd6d_aug_mask_stats  stats (B,max_id,5) int32 = {area, xmin, ymin, xmax, ymax} of mask == id (id 1..max_id);
+ *                      {0,0,0,0,0} when id is absent.  Integer atomics only (order-free).
+ * kd6d_aug_occlude     in place; per image the first min(n_inst[b], KD6D_MAX_GT) instances: rectangle from
+ *                      stats (stats_ids ids per image) and uniforms (B,KD6D_MAX_GT,5) double (RandomOcclusion's five
+ *                      random.uniform draws, as u in [0,1)); random bytes into the frame, -1 into the mask.
+ * kd6d_aug_hsv         in place; factors (B,3) float32 = the (h, s, v) multipliers of distort_hsv.
+ * kd6d_aug_filter      src -> dst (distinct): box blur ksize (B) int32 (odd, NULL = 1, BORDER_REFLECT_101), then
+ *                      Gaussian noise sigma (B) float32 (NULL or 0 = none), then BGR2GRAY into 3 channels if gray.
+ * kd6d_aug_relabel     in place; mask id in 1..max_id -> lut[b*(max_id+1) + id], any other value -> 0. */
+#define KD6D_AUG_MAX_ID 16
+int kd6d_aug_warp_u8(const uint8_t* src, const float* src_mask, int B, int H, int W, const double* fwd_mats, int Ho,
+                     int Wo, uint8_t* dst, float* dst_mask, void* stream);
+int kd6d_aug_mask_stats(const float* masks, int B, int H, int W, int max_id, int32_t* stats, void* stream);
+int kd6d_aug_occlude(uint8_t* frames, float* masks, int B, int H, int W, const int32_t* stats, int stats_ids,
+                     const double* uniforms, const int32_t* n_inst, double prob, uint64_t key, void* stream);
+int kd6d_aug_hsv(uint8_t* frames, int B, int H, int W, const float* factors, void* stream);
+int kd6d_aug_filter(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ksize, const float* sigma,
+                    int gray, uint64_t key, void* stream);
+int kd6d_aug_relabel(float* masks, int B, int H, int W, const float* lut, int max_id, void* stream);
 
 /* ---- optimiser: replaces clip_grad_norm_ + AdamW.step of train_kd.py:138-139 on one flat buffer.
  * kd6d_sumsq writes KD6D_SUMSQ_PARTS partial sums of x^2 (one per workgroup, unused slots zeroed; no atomics);

@@ -33,7 +33,9 @@ EXTRA_FLAGS = {"sinkhorn_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # network's convolutions, one HALF of a packed result occasionally came out as if its product were zero,
                # for the last 16 lanes of a wave (tests/flake_hunt.py); with scalar fp32 instructions it does not happen
                "losses.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-               "sinkhorn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "sinkhorn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # augment.hip runs in the loader, beside the other network's convolutions in pipelined mode: same switch
+               "augment.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

@@ -15,7 +15,7 @@ KD6D_F32 = 1
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 GN_STATS_READY, GN_WS_ZEROED = 1, 2
 MAX_SEG = 5
-ABI_VERSION = 9
+ABI_VERSION = 10
 ACC_ACT, ACC_GRAD = 32, 52           # KD6D_ACC_ACT / KD6D_ACC_GRAD: fixed-point classes of kd6d_acc
 NORM_GROUP, NORM_BATCH = 1, 2
 BN_FUSED_REPLICAS = 8
@@ -60,6 +60,7 @@ class BnIn(ctypes.Structure):
 
 
 MAX_GT = 4
+AUG_MAX_ID = 16                      # KD6D_AUG_MAX_ID: mask ids kd6d_aug_mask_stats / _relabel take
 MAX_ZERO = 8
 
 
@@ -154,6 +155,12 @@ SIGNATURES = {
     "kd6d_loss_backward": [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _F, _F, _I, _I,
                            _P, _P, _P],
     "kd6d_dzi_crop": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P],
+    "kd6d_aug_warp_u8": [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P],
+    "kd6d_aug_mask_stats": [_P, _I, _I, _I, _I, _P, _P],
+    "kd6d_aug_occlude": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _D, ctypes.c_uint64, _P],
+    "kd6d_aug_hsv": [_P, _I, _I, _I, _P, _P],
+    "kd6d_aug_filter": [_P, _P, _I, _I, _I, _P, _P, _I, ctypes.c_uint64, _P],
+    "kd6d_aug_relabel": [_P, _I, _I, _I, _P, _I, _P],
     "kd6d_sumsq": [_P, _I64, _P, _P],
     "kd6d_clip_adamw": [_P, _P, _P, _P, _I64, _P, _P, _D, _D, _D, _D, _D, _D, _I64, _P, _P, _P],
     "kd6d_set_hyper": [_P, _D, _D, _D, _I64, _P],

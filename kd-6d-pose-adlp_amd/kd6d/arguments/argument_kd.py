@@ -1,7 +1,7 @@
 """Command line + yaml -> (cfg, cfg_t): the flag surface of arguments/argument_kd.py:15-106.
 
 Every reference flag keeps its name, type and default.  Additive flags of this build:
---precision {bf16,fp32}, --synthetic, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
+--precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes; yaml files may name a `_BASE_` file.
 """
 import argparse
@@ -55,6 +55,9 @@ def get_argparser():
     # additive (this build)
     p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--synthetic", action="store_true", help="seeded LINEMOD-shaped synthetic batches (no dataset)")
+    p.add_argument("--augment", action="store_true",
+                   help="real data: run the reference's train transform chain (Resize, occlusion, shift-scale-rotate, HSV, "
+                        "blur, noise, grey, remove_invalids, symmetry handling) on the GPU front-end (kd6d/libs/augment.py)")
     p.add_argument("--skip_teacher_eval", action="store_true")
     p.add_argument("--launch", type=str, default="graph", choices=["graph", "pipeline", "eager"],
                    help="graph: replay the captured step (hipGraph); pipeline: also overlap the teacher forward of "
@@ -116,6 +119,7 @@ def build_cfgs(args):
     cfg["RUNTIME"] = _runtime(args, args.config_file, args.weight_file)
     cfg["RUNTIME"]["WORKING_DIR"] = args.working_dir
     cfg["RUNTIME"]["SYNTHETIC"] = bool(args.synthetic)
+    cfg["RUNTIME"]["AUGMENT"] = bool(getattr(args, "augment", False))
     cfg["RUNTIME"]["SKIP_TEACHER_EVAL"] = bool(args.skip_teacher_eval)
     cfg["RUNTIME"]["LAUNCH"] = args.launch
     cfg["RUNTIME"]["TEACHER_GROUP"] = max(1, int(args.teacher_group))

@@ -1,0 +1,342 @@
+"""Train-time augmentation of full frames (`train_kd.py --augment`): the reference's train transform chain
+(libs/train_libs.py:212-238) and its post-transform block (dataset.py:166-176), in the reference's order:
+
+  1 Resize                  M = INTERNAL_K K^-1; skipped when M is the identity (then a cv2 warp is an exact copy)
+  2 RandomOcclusion         AUGMENTATION_OCCLUSION
+  3 RandomShiftScaleRotate  AUGMENTATION_SHIFT / _SCALE / _ROTATION
+  4 RandomHSV               AUGMENTATION_ColorH / _ColorS / _ColorV
+  5 RandomSmooth            AUGMENTATION_Smooth (largest box size)
+  6 RandomNoise             AUGMENTATION_Noise
+  7 Grayscalize             AUGMENTATION_Grayscalize
+  8 remove_invalids(10)     instances under 10 visible pixels are dropped, mask ids renumbered 1..k
+  9 symmetry_handling       DATASETS.SYMMETRY_TYPES
+
+Split of the work:
+  * dataset item (`draw_params`, worker process): every scalar parameter, drawn with `random` as the reference
+    draws them, plus a 64-bit key for the per-pixel randomness; the two pose remaps (Resize, then SSR) with
+    kd6d.libs.pnp.remap_pose.  Occlusion takes a fixed block of five random.random() per instance slot; the device
+    maps them with random.uniform's own formula a + (b - a) u.
+  * `AugmentFront.run` (DziLoader, GPU): the pixel work in csrc/augment.hip, one readback of the (B, n) area table
+    (waited on with an event of the front-end's stream), the drop / relabel decision, symmetry handling.
+
+Deviations from the reference:
+  * the remap of an instance uses the 8 box corners of its CLASS (keypoints_3d[class_ids[i]]); PoseAnnot.transform
+    passes keypoints_3d[i], indexed by instance, which is only the class's box for class 0;
+  * an image that keeps no instance after the chain falls back to its frame after Resize only, with its
+    Resize-remapped pose (the reference draws another image instead);
+  * per-pixel random bytes / noise come from a counter-based hash on the device, not numpy's stream.
+RandomBackground and RandomPencilSharpen are not rebuilt: enabling them raises NotImplementedError.
+"""
+import random
+
+import numpy as np
+import torch
+
+from .._lib import AUG_MAX_ID, MAX_GT
+from .pnp import remap_pose
+
+MIN_AREA = 10
+
+
+class AugConfig:
+    """The augmentation keys of a yaml, with the reference's own enable guards."""
+
+    def __init__(self, cfg):
+        s, inp = cfg["SOLVER"], cfg["INPUT"]
+        if s.get("AUGMENTATION_BACKGROUND_DIR") is not None:
+            raise NotImplementedError("SOLVER.AUGMENTATION_BACKGROUND_DIR: RandomBackground is not rebuilt "
+                                      "for --augment")
+        if s.get("AUGMENTATION_Sharpen", 0):
+            raise NotImplementedError("SOLVER.AUGMENTATION_Sharpen: RandomPencilSharpen is not rebuilt for --augment")
+        self.K = np.array(inp["INTERNAL_K"], np.float64).reshape(3, 3)
+        self.width, self.height = int(inp["INTERNAL_WIDTH"]), int(inp["INTERNAL_HEIGHT"])
+        self.occlusion = float(s.get("AUGMENTATION_OCCLUSION", 0) or 0)
+        self.shift = float(s.get("AUGMENTATION_SHIFT", 0) or 0)
+        self.scale = float(s.get("AUGMENTATION_SCALE", 0) or 0)
+        self.rotation = float(s.get("AUGMENTATION_ROTATION", 0) or 0)
+        self.hsv = tuple(float(s.get(k, 0) or 0) for k in ("AUGMENTATION_ColorH", "AUGMENTATION_ColorS",
+                                                            "AUGMENTATION_ColorV"))
+        self.smooth = int(s.get("AUGMENTATION_Smooth", 0) or 0)
+        self.noise = float(s.get("AUGMENTATION_Noise", 0) or 0)
+        self.gray = bool(s.get("AUGMENTATION_Grayscalize", False))
+        self.symmetry_types = cfg["DATASETS"].get("SYMMETRY_TYPES") or {}
+
+    # the guards of transform.py
+    @property
+    def occlusion_on(self):
+        return self.occlusion > 0
+
+    @property
+    def ssr_on(self):
+        return (self.shift + self.scale + self.rotation) > 0.01
+
+    @property
+    def hsv_on(self):
+        return sum(self.hsv) > 0.01
+
+    @property
+    def smooth_on(self):
+        return self.smooth > 1
+
+    @property
+    def noise_on(self):
+        return self.noise > 0.01
+
+
+def resize_matrix(dst_K, src_K):
+    """transform.Resize: M = dst_K inv(src_K) (3x3, float64)."""
+    return np.matmul(np.asarray(dst_K, np.float64).reshape(3, 3), np.linalg.inv(np.asarray(src_K, np.float64).reshape(3, 3)))
+
+
+def is_identity_warp(M, width, height, tol=1e-6):
+    """True when M moves no pixel of a width x height frame by more than tol px (far below cv2's 1/1024 px step):
+    the cv2 8-bit warp is then an exact copy."""
+    M = np.asarray(M, np.float64)
+    pts = np.array([[0, 0, 1], [width, 0, 1], [0, height, 1], [width, height, 1]], np.float64).T
+    return bool(np.abs(M[:2] @ pts - pts[:2]).max() < tol)
+
+
+def rotation_matrix_2d(center, angle, scale):
+    """cv2.getRotationMatrix2D from its documented formula (degrees, counter-clockwise)."""
+    a = np.deg2rad(angle)
+    alpha, beta = np.cos(a) * scale, np.sin(a) * scale
+    cx, cy = center
+    return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]])
+
+
+def shift_scale_rotate_matrix(shift_limit, scale_limit, rotate_limit, width, height, rng=random):
+    """utils.py:161-179 generate_shiftscalerotate_matrix: draws randint, randint, uniform, uniform in that order;
+    3x3, cast to float32 like the reference."""
+    dw, dh = int(width * shift_limit), int(height * shift_limit)
+    pleft = rng.randint(-dw, dw)
+    ptop = rng.randint(-dh, dh)
+    shiftM = np.array([[1.0, 0.0, -pleft], [0.0, 1.0, -ptop], [0.0, 0.0, 1.0]])
+    cx, cy = width / 2, height / 2
+    ang = rng.uniform(-rotate_limit, rotate_limit)
+    sfactor = rng.uniform(-scale_limit, +scale_limit) + 1
+    rsM = np.concatenate((rotation_matrix_2d((cx, cy), ang, sfactor), [[0, 0, 1]]), axis=0)
+    return np.matmul(rsM, shiftM).astype(np.float32)
+
+
+def remap_poses(K, class_ids, rotations, translations, bbox_3d, dst_K, M):
+    """PoseAnnot.transform's pose part with the CLASS's box corners as the remap points."""
+    Rs, Ts = [], []
+    for i, c in enumerate(class_ids):
+        R, T, _ = remap_pose(K, rotations[i], translations[i], np.asarray(bbox_3d[int(c)], np.float64), dst_K,
+                             np.asarray(M, np.float64))
+        Rs.append(np.asarray(R, np.float32).reshape(3, 3))
+        Ts.append(np.asarray(T, np.float32).reshape(3, 1))
+    return np.asarray(Rs, np.float32).reshape(-1, 3, 3), np.asarray(Ts, np.float32).reshape(-1, 3, 1)
+
+
+def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random):
+    """Everything random of one item, in the chain's order, and the two pose remaps.  -> dict."""
+    n = len(class_ids)
+    if n > AUG_MAX_ID:
+        raise ValueError("--augment handles at most %d instances per frame (got %d)" % (AUG_MAX_ID, n))
+    p = {}
+    Mr = resize_matrix(ac.K, K)
+    p["M_resize"] = Mr[:2].copy()
+    p["R_resize"], p["T_resize"] = remap_poses(K, class_ids, rotations, translations, bbox_3d, ac.K, Mr)
+    if ac.occlusion_on:
+        p["occl_u"] = np.array([[rng.random() for _ in range(5)] for _ in range(MAX_GT)], np.float64)
+    if ac.ssr_on:
+        Ms = shift_scale_rotate_matrix(ac.shift, ac.scale, ac.rotation, ac.width, ac.height, rng)
+        p["M_ssr"] = Ms[:2].astype(np.float64)
+        p["R"], p["T"] = remap_poses(ac.K, class_ids, p["R_resize"], p["T_resize"], bbox_3d, ac.K, Ms)
+    else:
+        p["R"], p["T"] = p["R_resize"], p["T_resize"]
+    if ac.hsv_on:
+        p["hsv"] = np.array([rng.uniform(-1, 1) * r + 1 for r in ac.hsv], np.float32)
+    if ac.smooth_on:
+        p["ksize"] = rng.choice(list(range(1, ac.smooth + 1, 2)))
+    if ac.noise_on:
+        p["sigma"] = rng.uniform(0, ac.noise)
+    p["key"] = rng.getrandbits(64)
+    p["n"] = n
+    return p
+
+
+def collate_params(ps):
+    """list of draw_params dicts -> one dict of stacked arrays (per-instance poses stay lists)."""
+    out = {"M_resize": np.stack([p["M_resize"] for p in ps]), "n": np.array([p["n"] for p in ps], np.int32),
+           "key": np.array([p["key"] for p in ps], np.uint64)}
+    for k in ("R_resize", "T_resize", "R", "T"):
+        out[k] = [p[k] for p in ps]
+    if "occl_u" in ps[0]:
+        out["occl_u"] = np.stack([p["occl_u"] for p in ps])
+    if "M_ssr" in ps[0]:
+        out["M_ssr"] = np.stack([p["M_ssr"] for p in ps])
+    if "hsv" in ps[0]:
+        out["hsv"] = np.stack([p["hsv"] for p in ps]).astype(np.float32)
+    if "ksize" in ps[0]:
+        out["ksize"] = np.array([p["ksize"] for p in ps], np.int32)
+    if "sigma" in ps[0]:
+        out["sigma"] = np.array([p["sigma"] for p in ps], np.float32)
+    return out
+
+
+def batch_key(keys):
+    """One 64-bit launch key from the items' keys (the device hash also mixes in the image index)."""
+    k = 0
+    for v in np.asarray(keys, np.uint64).tolist():
+        k = (k * 0x100000001B3 ^ int(v)) & 0xFFFFFFFFFFFFFFFF
+    return k
+
+
+# ---- thin launch wrappers (device tensors in, asynchronous on the current stream) --------------------------------
+def _dev(a, dtype, device):
+    return torch.as_tensor(np.ascontiguousarray(a)).to(device=device, dtype=dtype, non_blocking=False).contiguous()
+
+
+def warp(frames, masks, mats, out_hw):
+    """frames (B,H,W,3) uint8, masks (B,H,W) float32 or None, mats (B,2,3) forward matrices (host) -> warped."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W, _ = frames.shape
+    Ho, Wo = out_hw
+    dev = frames.device
+    m = _dev(np.asarray(mats, np.float64).reshape(B, 6), torch.float64, dev)
+    out = torch.empty(B, Ho, Wo, 3, dtype=torch.uint8, device=dev)
+    mout = torch.empty(B, Ho, Wo, dtype=torch.float32, device=dev) if masks is not None else None
+    check(lib.kd6d_aug_warp_u8(ops._ptr(frames), ops._ptr(masks), B, H, W, ops._ptr(m), Ho, Wo, ops._ptr(out),
+                               ops._ptr(mout), ops._stream()), "kd6d_aug_warp_u8")
+    return out, mout
+
+
+def mask_stats(masks, max_id):
+    """-> (B, max_id, 5) int32 device tensor {area, xmin, ymin, xmax, ymax}."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W = masks.shape
+    st = torch.empty(B, max_id, 5, dtype=torch.int32, device=masks.device)
+    check(lib.kd6d_aug_mask_stats(ops._ptr(masks), B, H, W, max_id, ops._ptr(st), ops._stream()), "kd6d_aug_mask_stats")
+    return st
+
+
+def occlude(frames, masks, stats, uniforms, n_inst, prob, key):
+    """In place.  uniforms (B, MAX_GT, 5) host, n_inst (B,) host."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W, _ = frames.shape
+    dev = frames.device
+    u = _dev(np.asarray(uniforms, np.float64).reshape(B, MAX_GT, 5), torch.float64, dev)
+    n = _dev(np.asarray(n_inst, np.int32).reshape(B), torch.int32, dev)
+    check(lib.kd6d_aug_occlude(ops._ptr(frames), ops._ptr(masks), B, H, W, ops._ptr(stats), stats.shape[1], ops._ptr(u),
+                               ops._ptr(n), float(prob), int(key), ops._stream()), "kd6d_aug_occlude")
+
+
+def hsv(frames, factors):
+    """In place.  factors (B,3) float32 host."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W, _ = frames.shape
+    f = _dev(np.asarray(factors, np.float32).reshape(B, 3), torch.float32, frames.device)
+    check(lib.kd6d_aug_hsv(ops._ptr(frames), B, H, W, ops._ptr(f), ops._stream()), "kd6d_aug_hsv")
+
+
+def filt(frames, ksize=None, sigma=None, gray=False, key=0):
+    """-> new buffer: blur (ksize (B,) or None), noise (sigma (B,) or None), grayscale."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W, _ = frames.shape
+    dev = frames.device
+    k = _dev(np.asarray(ksize, np.int32).reshape(B), torch.int32, dev) if ksize is not None else None
+    s = _dev(np.asarray(sigma, np.float32).reshape(B), torch.float32, dev) if sigma is not None else None
+    out = torch.empty_like(frames)
+    check(lib.kd6d_aug_filter(ops._ptr(frames), ops._ptr(out), B, H, W, ops._ptr(k), ops._ptr(s), int(bool(gray)),
+                              int(key), ops._stream()), "kd6d_aug_filter")
+    return out
+
+
+def relabel(masks, lut):
+    """In place.  lut (B, max_id + 1) host float32."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W = masks.shape
+    lut = np.asarray(lut, np.float32)
+    L = _dev(lut, torch.float32, masks.device)
+    check(lib.kd6d_aug_relabel(ops._ptr(masks), B, H, W, ops._ptr(L), lut.shape[1] - 1, ops._stream()),
+          "kd6d_aug_relabel")
+
+
+class AugmentFront:
+    """The GPU half of --augment, run by DziLoader on each training batch."""
+
+    def __init__(self, ac, device):
+        self.ac, self.device = ac, device
+
+    def run(self, frames, masks, targets, params):
+        """frames (B,H,W,3) uint8 / masks (B,H,W) float32 on the device, the items' original PoseAnnots, collated
+        params -> (frames, masks at the internal size, per image (class_ids, R (n,3,3), T (n,3,1)) after
+        remove_invalids + symmetry handling)."""
+        ac = self.ac
+        B, H, W, _ = frames.shape
+        key = batch_key(params["key"])
+        size = (ac.height, ac.width)
+        # 1 Resize
+        if (H, W) == size and all(is_identity_warp(np.vstack([m, [0, 0, 1]]), W, H) for m in params["M_resize"]):
+            resized, resized_m = frames, masks
+        else:
+            resized, resized_m = warp(frames, masks, params["M_resize"], size)
+        cur, cur_m = resized, resized_m
+        n_inst = params["n"]
+        max_id = max(int(n_inst.max()) if B else 0, 1)
+        # 2 RandomOcclusion (visible boxes of the resized mask, taken once)
+        if ac.occlusion_on:
+            cur, cur_m = cur.clone(), cur_m.clone()          # the resized frame is kept for the fallback
+            st = mask_stats(cur_m, max(max_id, MAX_GT))
+            occlude(cur, cur_m, st, params["occl_u"], n_inst, ac.occlusion, key)
+        # 3 RandomShiftScaleRotate
+        if ac.ssr_on:
+            cur, cur_m = warp(cur, cur_m, params["M_ssr"], size)
+        # 4 RandomHSV
+        if ac.hsv_on:
+            if cur is resized:
+                cur = cur.clone()
+            hsv(cur, params["hsv"])
+        # 5-7 RandomSmooth, RandomNoise, Grayscalize
+        if ac.smooth_on or ac.noise_on or ac.gray:
+            cur = filt(cur, params.get("ksize"), params.get("sigma"), ac.gray, key)
+        if cur_m is resized_m:
+            cur_m = cur_m.clone()
+        # 8 remove_invalids: one small readback, waited on with an event of this stream
+        st = mask_stats(cur_m, max_id)
+        host = torch.empty(st.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(st, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+        area = host[:, :, 0].numpy()
+        lut = np.zeros((B, max_id + 1), np.float32)
+        out = []
+        fallback = []
+        for b in range(B):
+            n = int(n_inst[b])
+            cls = targets[b].class_ids.numpy()[:n]
+            keep = [i for i in range(n) if area[b, i] >= MIN_AREA]
+            if keep:
+                for j, i in enumerate(keep):
+                    lut[b, i + 1] = j + 1
+                R, T = params["R"][b][keep], params["T"][b][keep]
+                cls = cls[keep]
+            else:
+                # deliberate deviation: the reference draws another image; this one falls back to Resize only
+                fallback.append(b)
+                lut[b, 1:n + 1] = np.arange(1, n + 1, dtype=np.float32)
+                R, T = params["R_resize"][b], params["T_resize"][b]
+            R = np.asarray(R, np.float32).copy()
+            for i, c in enumerate(cls):
+                k = "cls_" + str(int(c))
+                if k in ac.symmetry_types:
+                    from .evaluate import pose_symmetry_handling
+                    R[i] = pose_symmetry_handling(R[i], ac.symmetry_types[k])
+            out.append((cls.astype(np.int64), R, np.asarray(T, np.float32)))
+        if fallback:
+            idx = torch.tensor(fallback, dtype=torch.long, device=cur.device)
+            if cur is resized:
+                cur = cur.clone()
+            cur[idx] = resized[idx]
+            cur_m[idx] = resized_m[idx]
+        relabel(cur_m, lut)
+        return cur, cur_m, out

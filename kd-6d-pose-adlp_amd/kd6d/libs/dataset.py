@@ -9,8 +9,10 @@ white background).  Frames come back as BGR uint8 (the reference's cv2 order) so
 (`kd6d/libs/dzi_libs.dzi_batch`, csrc/dzi.hip) can crop + normalise them; `collate_frames` stacks a batch of
 equal-size frames and derives the DZI boxes from the projected 3D boxes like `dzi_libs.py:142-210`.
 
-Not rebuilt: the CPU augmentation pipeline of libs/transform.py (resize / colour jitter / occlusion with cv2 and
-imgaug) -- frames must already have the internal resolution -- and `remap_predictions`.
+The train transform chain of libs/transform.py (Resize, occlusion, shift-scale-rotate, colour jitter, blur, noise,
+grey) is opt-in (`augment=`, train_kd.py --augment): an item then also carries the scalar draws and remapped poses
+of kd6d/libs/augment.py, and the pixel work runs on the GPU (csrc/augment.hip).  Without it, frames must already
+have the internal resolution.
 Decoding uses Pillow; **parity unpinned** against cv2.imread for exotic PNG variants (checked: 8-bit RGB / RGBA /
 grey and 16-bit grey, the formats BOP ships).
 """
@@ -167,7 +169,10 @@ class BOP_Dataset(torch.utils.data.Dataset):
     dataset.py:71-103 before the transform; the crop + normalisation happen on the GPU (`collate_frames` +
     `dzi_libs.dzi_batch`)."""
 
-    def __init__(self, image_list_file, mesh_dir, bbox_json, symmetry_types=None, training=True, mem_cache=None):
+    def __init__(self, image_list_file, mesh_dir, bbox_json, symmetry_types=None, training=True, mem_cache=None,
+                 augment=False):
+        """augment: False, or the training cfg (or a kd6d.libs.augment.AugConfig): items then carry a fourth element,
+        the augmentation parameters (augment.draw_params) drawn with `random`."""
         data_dir = os.path.split(image_list_file)[0]
         with open(image_list_file, "r") as f:
             files = [ln.strip() for ln in f.readlines() if ln.strip()]
@@ -179,6 +184,10 @@ class BOP_Dataset(torch.utils.data.Dataset):
         self.symmetry_types = symmetry_types
         self.training = training
         self.cache = mem_cache
+        self.augment = None
+        if augment is not False and augment is not None:
+            from .augment import AugConfig
+            self.augment = augment if isinstance(augment, AugConfig) else AugConfig(augment)
 
     def __len__(self):
         return len(self.img_files)
@@ -206,7 +215,12 @@ class BOP_Dataset(torch.utils.data.Dataset):
                            torch.tensor(class_ids, dtype=torch.long),
                            torch.tensor(np.asarray(rotations, np.float32).reshape(-1, 3, 3)),
                            torch.tensor(np.asarray(translations, np.float32).reshape(-1, 3, 1)), w, h)
-        return torch.from_numpy(np.ascontiguousarray(img[:, :, :3])), target, meta
+        frame = torch.from_numpy(np.ascontiguousarray(img[:, :, :3]))
+        if self.augment is None:
+            return frame, target, meta
+        from .augment import draw_params
+        params = draw_params(self.augment, K, class_ids, rotations, translations, self.bbox_3d.numpy())
+        return frame, target, meta, params
 
 
 def projected_box(target, g=0):
@@ -220,7 +234,12 @@ def projected_box(target, g=0):
 
 
 def collate_frames(batch):
-    """list of dataset items (equal frame size) -> (frames (B,H,W,3) uint8, masks (B,H,W) float32, targets, metas)."""
+    """list of dataset items (equal frame size) -> (frames (B,H,W,3) uint8, masks (B,H,W) float32, targets, metas),
+    plus the stacked augmentation parameters (augment.collate_params) when the items carry them."""
     frames = torch.stack([b[0] for b in batch]).contiguous()
     masks = torch.stack([b[1].mask for b in batch]).contiguous()
-    return frames, masks, [b[1] for b in batch], [b[2] for b in batch]
+    out = (frames, masks, [b[1] for b in batch], [b[2] for b in batch])
+    if len(batch[0]) == 4:
+        from .augment import collate_params
+        out = out + (collate_params([b[3] for b in batch]),)
+    return out

@@ -122,13 +122,20 @@ class DziLoader:
     (libs/dzi_libs.py:55-140) and `collate_fn`: (ImageList of 256x256 normalised crops, targets with the cropped mask,
     bbox_trans and bbox_scale, meta_infos).  Normalize + the affine crop of image and mask run as ONE kd6d_dzi_crop
     launch per batch on the GPU; the three jitter numbers per image come from numpy's global RNG like the reference.
-    The CPU augmentation chain of libs/transform.py is not rebuilt: frames must already have the internal resolution."""
+    Without `augment`, frames must already have the internal resolution.  With `augment=True` (train_kd.py --augment;
+    the dataset must have been built with augment too) the reference's train transform chain -- Resize to INTERNAL_K,
+    occlusion, shift-scale-rotate, HSV, blur, noise, grey, remove_invalids(10), symmetry handling -- runs first,
+    on the GPU (kd6d/libs/augment.py, csrc/augment.hip), and the crop box comes from the remapped pose."""
 
-    def __init__(self, loader, cfg, device, training):
+    def __init__(self, loader, cfg, device, training, augment=False):
         from .dzi_libs import normalize_lut
         self.loader, self.cfg, self.device, self.training = loader, cfg, device, training
         self.lut = normalize_lut(cfg["INPUT"]["PIXEL_MEAN"], cfg["INPUT"]["PIXEL_STD"], device)
         self.size = (cfg["INPUT"]["INTERNAL_HEIGHT"], cfg["INPUT"]["INTERNAL_WIDTH"])
+        self.front = None
+        if augment:
+            from .augment import AugConfig, AugmentFront
+            self.front = AugmentFront(AugConfig(cfg), device)
 
     def __len__(self):
         return len(self.loader)
@@ -138,6 +145,9 @@ class DziLoader:
         from .dataset import projected_box
         from .dzi_libs import aug_bbox_DZI, dzi_batch, test_bbox_DZI
         from .poses import ImageList, PoseAnnot
+        if self.front is not None:
+            yield from self._iter_augment()
+            return
         for frames, masks, targets, metas in self.loader:
             B, H, W, _ = frames.shape
             if (H, W) != tuple(self.size):
@@ -159,21 +169,57 @@ class DziLoader:
                              t.translations.to(dev), R, R, bscale[i], trans[i]) for i, t in enumerate(targets)]
             yield ImageList(images, [(R, R)] * B), PackedTargets(out, dev), metas
 
+    def _iter_augment(self):
+        from ..kd_losses import PackedTargets
+        from .dataset import projected_box
+        from .dzi_libs import aug_bbox_DZI, dzi_batch, test_bbox_DZI
+        from .poses import ImageList, PoseAnnot
+        dev = self.device
+        K = torch.tensor(self.front.ac.K, dtype=torch.float32)
+        H, W = self.size
+        for batch in self.loader:
+            if len(batch) != 5:
+                raise ValueError("DziLoader(augment=True) needs a dataset built with augment (BOP_Dataset(augment=cfg))")
+            frames, masks, targets, metas, params = batch
+            frames, masks, poses = self.front.run(frames.to(dev, non_blocking=True).contiguous(),
+                                                  masks.to(dev, non_blocking=True).contiguous(), targets, params)
+            B = frames.shape[0]
+            annots, centers, scales = [], [], []
+            for t, (cls, Rs, Ts) in zip(targets, poses):
+                a = PoseAnnot(t.keypoints_3d, K, None, torch.from_numpy(cls), torch.from_numpy(Rs).reshape(-1, 3, 3),
+                              torch.from_numpy(Ts).reshape(-1, 3, 1), W, H)
+                box = projected_box(a, 0) if len(cls) else np.array([0.0, 0.0, float(W), float(H)])
+                c, s = aug_bbox_DZI(box, H, W) if self.training else test_bbox_DZI(box, H, W)
+                centers.append(c); scales.append(s)
+                annots.append(a)
+            images, crop_masks, trans, bscale = dzi_batch(frames, masks, np.stack(centers), np.asarray(scales), self.lut)
+            R = images.shape[-1]
+            out = [PoseAnnot(a.keypoints_3d.to(dev), a.K.to(dev), crop_masks[i], a.class_ids.to(dev), a.rotations.to(dev),
+                             a.translations.to(dev), R, R, bscale[i], trans[i]) for i, a in enumerate(annots)]
+            yield ImageList(images, [(R, R)] * B), PackedTargets(out, dev), metas
 
-def build_dataset(cfg, device="cuda"):
+
+def build_dataset(cfg, device="cuda", augment=False):
     """libs/train_libs.py:209-291: (train_loader, valid_loader) over the BOP image lists of cfg['DATASETS'], batch
     = IMS_PER_BATCH / N_GPU per rank, DistributedSampler semantics of libs/distributed.py.  DATASETS.TRAIN may be one
-    list file or several (configs/linemod13.yaml): the datasets are concatenated."""
+    list file or several (configs/linemod13.yaml): the datasets are concatenated.  augment=True runs the reference's
+    train transform chain on the training batches (DziLoader); the valid loader is untouched."""
     from torch.utils.data import ConcatDataset, DataLoader
     from .dataset import BOP_Dataset, collate_frames
     ds = cfg["DATASETS"]
 
-    def make(files, training):
+    aug = False
+    if augment:
+        from .augment import AugConfig
+        aug = AugConfig(cfg)                 # raises NotImplementedError for the transforms that are not rebuilt
+
+    def make(files, training, augment=False):
         files = [files] if isinstance(files, str) else list(files)
-        sets = [BOP_Dataset(f, ds["MESH_DIR"], ds["BBOX_FILE"], ds.get("SYMMETRY_TYPES"), training=training) for f in files]
+        sets = [BOP_Dataset(f, ds["MESH_DIR"], ds["BBOX_FILE"], ds.get("SYMMETRY_TYPES"), training=training,
+                            augment=augment) for f in files]
         return sets[0] if len(sets) == 1 else ConcatDataset(sets)
 
-    train_set, valid_set = make(ds["TRAIN"], True), make(ds["VALID"], False)
+    train_set, valid_set = make(ds["TRAIN"], True, aug), make(ds["VALID"], False)
     per_gpu = D.shard_batch(cfg["SOLVER"]["IMS_PER_BATCH"])
     dist_on = cfg["RUNTIME"].get("DISTRIBUTED", False)
 
@@ -187,7 +233,8 @@ def build_dataset(cfg, device="cuda"):
         return DataLoader(dset, batch_size=per_gpu, sampler=smp, num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0),
                           collate_fn=collate_frames, drop_last=shuffle)
 
-    return DziLoader(loader(train_set, True), cfg, device, True), DziLoader(loader(valid_set, False), cfg, device, False)
+    return (DziLoader(loader(train_set, True), cfg, device, True, augment=bool(augment)),
+            DziLoader(loader(valid_set, False), cfg, device, False))
 
 
 def dataset_meshes(loader):

@@ -8,7 +8,8 @@ train_kd.py:34-171, on the MI355X-native kd6d step.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N train_kd.py ...  (one process per
 GPU; the gradient exchange goes through kd6d_comm_* = librccl over xGMI).  Without --synthetic the BOP / LINEMOD
 image lists of the yaml are read (kd6d/libs/train_libs.build_dataset: frames at the internal resolution, the
-Dynamic-Zoom-In crop + normalisation run on the GPU); with it, seeded LINEMOD-shaped batches.  As in the
+Dynamic-Zoom-In crop + normalisation run on the GPU; --augment adds the reference's train transform chain, Resize to
+INTERNAL_K included, on the GPU front-end); with it, seeded LINEMOD-shaped batches.  As in the
 reference the teacher is validated once before training (skip with --skip_teacher_eval) and every VAL_FREQ steps
 rank 0 validates the student (kd6d/libs/eval_libs.valid: eval forward -> pose candidates -> PnP-RANSAC -> ADI /
 REP) and writes latest.pth.  Scalars go to tensorboardX under the reference's tags when that package is
@@ -150,7 +151,8 @@ if __name__ == "__main__":
         train_loader = synthetic_loader(cfg, device)
         valid_loader, valid_meshes = synthetic_valid_loader(cfg, device)
     else:
-        train_loader, valid_loader = build_dataset(cfg, device)               # train_kd.py:57 of the reference
+        train_loader, valid_loader = build_dataset(cfg, device,                # train_kd.py:57 of the reference
+                                                   augment=cfg["RUNTIME"].get("AUGMENT", False))
         valid_meshes = dataset_meshes(valid_loader)
 
         def epochs(loader):                                                    # the reference loops `while True` over epochs
