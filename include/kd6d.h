@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define KD6D_ABI_VERSION 10
+#define KD6D_ABI_VERSION 11
 
 enum { KD6D_BF16 = 0, KD6D_F32 = 1 };
 enum { KD6D_ACT_NONE = 0, KD6D_ACT_LEAKY = 1, KD6D_ACT_RELU = 2 };
@@ -489,6 +489,29 @@ int kd6d_pose_candidates(const kd6d_levels* levels, const float* cls, const floa
                          const float* bbox_trans, const int32_t* class_ids, const int32_t* n_gt,
                          float threshold, float positive_num, float positive_lambda, int cap,
                          int32_t* cnt, float* kp, float* score, void* stream);
+/* ---- PnP-RANSAC on the device (csrc/pnp.hip): kd6d/libs/pnp.py's solve_pnp_ransac for a batch of problems.
+ * Problem p: cnt[p] <= cap cells (cap <= KD6D_PNP_MAX_CAP), kp (P*cap, 8, 2) full-frame px with problem p's cells at
+ * p*cap (the layout of t_kp and of kd6d_pose_candidates' kp), box (P, 8, 3) object-space corners, K (P, 3, 3);
+ * correspondence (cell i, keypoint k) belongs to corner k.  `iters` hypotheses, each one cell per corner drawn by a
+ * counter-based hash of (seed, h, k): DLT, loose consensus (3 x reproj_err, z > 0), DLT re-fit on it, 4 Gauss-Newton
+ * steps, tight consensus (reproj_err), 6 more steps when that set holds >= 6 points on >= 6 corners.  The winner has
+ * the most tight inliers (ties: the smallest h).  Outputs: ok[p] = (winner's count >= 6, R and T finite), R (P,3,3),
+ * T (P,3), n_inliers[p]; all zero when !ok (cnt[p] == 0, a box with < 6 distinct corners, a non-finite input).  A pure
+ * function of the problem's own inputs and `seed`: bitwise reproducible, independent of the batch around it.
+ * workspace: kd6d_pnp_workspace_floats(P, iters) floats, any contents.
+ * kd6d_teacher_pnp_gate: the gate of postprocess_kd.py:187-202 on kd6d_teacher_select's slot arrays.  For every image
+ * b with t_cnt[b] > 0 the class c is the first c < n_cls with sigmoid(cls[t_row[b*cap]*16 + c]) > threshold, else the
+ * argmax; the problem is (image b's t_kp cells, kp3d[b, c] of kp3d (batch, n_class_rows, 8, 3), K[b]); t_cnt[b] = 0
+ * when no pose is found (written by the launch's last kernel only). */
+#define KD6D_PNP_MAX_CAP 32
+int64_t kd6d_pnp_workspace_floats(int n_problems, int iters);
+int kd6d_pnp_ransac(int n_problems, int cap, const int32_t* cnt, const float* kp, const float* box, const float* K,
+                    float reproj_err, int iters, uint64_t seed, int32_t* ok, float* R, float* T, int32_t* n_inliers,
+                    float* workspace, int64_t workspace_floats, void* stream);
+int kd6d_teacher_pnp_gate(const float* cls, int n_cls, float threshold, const int32_t* t_row, int32_t* t_cnt,
+                          const float* t_kp, int cap, int batch, const float* kp3d, int n_class_rows, const float* K,
+                          float reproj_err, int iters, uint64_t seed, float* workspace, int64_t workspace_floats,
+                          void* stream);
 int kd6d_ssc_assign(const kd6d_levels* levels, const float* mask, int mask_h, int mask_w, const float* kp3d,
                     const float* K, const int32_t* class_ids, const int32_t* n_gt, const float* rot,
                     const float* trans, const float* bbox_trans, const float* keys, float positive_num,

@@ -15,7 +15,7 @@ KD6D_F32 = 1
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 GN_STATS_READY, GN_WS_ZEROED = 1, 2
 MAX_SEG = 5
-ABI_VERSION = 10
+ABI_VERSION = 11
 ACC_ACT, ACC_GRAD = 32, 52           # KD6D_ACC_ACT / KD6D_ACC_GRAD: fixed-point classes of kd6d_acc
 NORM_GROUP, NORM_BATCH = 1, 2
 BN_FUSED_REPLICAS = 8
@@ -146,6 +146,9 @@ SIGNATURES = {
     "kd6d_sinkhorn_dense_fwd_bwd": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _D, _P, _I64, _P, _P, _P, _P],
     "kd6d_teacher_select": [_L, _P, _P, _P, _F, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P],
     "kd6d_pose_candidates": [_L, _P, _P, _P, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P],
+    "kd6d_pnp_workspace_floats": [_I, _I],
+    "kd6d_pnp_ransac": [_I, _I, _P, _P, _P, _P, _F, _I, ctypes.c_uint64, _P, _P, _P, _P, _P, _I64, _P],
+    "kd6d_teacher_pnp_gate": [_P, _I, _F, _P, _P, _P, _I, _I, _P, _I, _P, _F, _I, ctypes.c_uint64, _P, _I64, _P],
     "kd6d_ssc_assign": [_L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P],
     "kd6d_focal_fwd": [_P, _P, _I, _F, _F, _P, _P, _P],
     "kd6d_focal_bwd": [_I, _P, _P, _I, _F, _F, _P, _P, _P],

@@ -477,7 +477,15 @@ class GroupedTeacherKDStep(GraphedKDStep):
         big = object.__new__(PackedTargets)                                       # what the teacher reads of the targets
         big.bbox_trans = torch.zeros((T * B,) + tuple(tgt.bbox_trans.shape[1:]), dtype=torch.float32, device=dev)
         big.frame_wh = tgt.frame_wh
+        if self._gate_reads_targets():
+            # the teacher PnP gate also reads every image's intrinsics and 3D boxes
+            big.K = torch.zeros((T * B,) + tuple(tgt.K.shape[1:]), dtype=torch.float32, device=dev)
+            big.kp3d = torch.zeros((T * B,) + tuple(tgt.kp3d.shape[1:]), dtype=torch.float32, device=dev)
         self._tgt_big = big
+
+    def _gate_reads_targets(self):
+        """The teacher's PnP gate on (PoseModuleKD.teacher_pnp_gate): the group pass reads K and kp3d too."""
+        return bool(getattr(self.teacher, "teacher_pnp_gate", False))
 
     def _slot_rows(self, s):
         B, H, W = self._geom
@@ -532,8 +540,12 @@ class GroupedTeacherKDStep(GraphedKDStep):
         B = self._geom[0]
         P, tnet = self.sides[1], self.teacher.net
         ops.mark("teacher.start")
+        gate = self._gate_reads_targets()
         for s in range(T):
             self._tgt_big.bbox_trans[s * B:(s + 1) * B].copy_(P.tgts[s].bbox_trans, non_blocking=True)
+            if gate:
+                self._tgt_big.K[s * B:(s + 1) * B].copy_(P.tgts[s].K, non_blocking=True)
+                self._tgt_big.kp3d[s * B:(s + 1) * B].copy_(P.tgts[s].kp3d, non_blocking=True)
         tnet.nhwc_in = P.nhwc
         keep = getattr(self.teacher, "_teacher_flats", None)
         self.teacher._teacher_flats = (P.wf, P.wi)

@@ -179,6 +179,18 @@ def solve_pnp_ransac(xyz, uv, K, reproj_err=5.0, iters=300, seed=0):
     return True, R.astype(np.float32), T.reshape(3, 1).astype(np.float32), np.nonzero(inl)[0]
 
 
+def solve_pnp_ransac_device(kp, cnt, box, K, reproj_err=5.0, iters=300, seed=0, workspace=None):
+    """solve_pnp_ransac for a batch of problems in one launch on the GPU (csrc/pnp.hip, the same structure: one cell
+    per corner per hypothesis, DLT, loose consensus, DLT re-fit, Gauss-Newton, tight consensus; counter-based
+    sampling instead of numpy's generator, so the two solvers agree on clear-cut problems, not hypothesis by
+    hypothesis).  Problem p owns kp[p*cap:(p+1)*cap] (cells, 8, 2) px of which the first cnt[p] count; correspondence
+    (cell, keypoint k) belongs to box[p, k].  kp (P*cap, 8, 2), cnt (P,) int32, box (P, 8, 3), K (P, 3, 3): contiguous
+    fp32 / int32 device tensors.  -> (ok (P,) int32, R (P,3,3), T (P,3), n_inliers (P,) int32) on the device, without
+    synchronising; bitwise reproducible and independent of the batch around a problem."""
+    from .. import ops
+    return ops.pnp_ransac(kp, cnt, box, K, reproj_err=reproj_err, iters=iters, seed=seed, workspace=workspace)
+
+
 def solve_pnp(xyz, uv, K):
     """cv2.solvePnP without RANSAC for clean correspondences (libs/utils.py:511 uses SOLVEPNP_EPNP): direct linear
     transform + Gauss-Newton.  -> (ok, R (3,3), T (3,1))."""

@@ -59,8 +59,14 @@ class PoseModuleKD(nn.Module):
             "cfg FEAT_CHANNELS/OUT_CHANNEL do not match backbone %s" % arch
         self.inference_th = cfg["TEST"]["CONFIDENCE_TH"]
         from ..postprocess import PostProcessor
+        # cfg['RUNTIME']['PNP_SOLVER'] (--pnp_solver): "host" = kd6d/libs/pnp.py, "device" = csrc/pnp.hip (the eval
+        # path solves every object of a batch in one launch; the teacher gate becomes capturable)
+        self.pnp_solver = cfg.get("RUNTIME", {}).get("PNP_SOLVER", "host")
+        if self.pnp_solver not in ("host", "device"):
+            raise ValueError("RUNTIME.PNP_SOLVER must be 'host' or 'device', got %r" % (self.pnp_solver,))
         self.post_processor = PostProcessor(cfg["TEST"]["CONFIDENCE_TH"], cfg["SOLVER"]["POSITIVE_NUM"],
-                                            cfg["SOLVER"]["POSITIVE_LAMBDA"], cfg["DATASETS"].get("SYMMETRY_TYPES", {}))
+                                            cfg["SOLVER"]["POSITIVE_LAMBDA"], cfg["DATASETS"].get("SYMMETRY_TYPES", {}),
+                                            solver=self.pnp_solver)
         self.positive_num = cfg["SOLVER"]["POSITIVE_NUM"]
         self.positive_lambda = cfg["SOLVER"]["POSITIVE_LAMBDA"]
         if cfg["SOLVER"]["POSITIVE_TYPE"] != "SSC" or cfg["SOLVER"]["LOSS_REG_TYPE"] != "3D" or \
@@ -72,7 +78,8 @@ class PoseModuleKD(nn.Module):
         # postprocess_kd.py:187-202: the reference runs RANSAC-EPnP on a teacher's selected cells and keeps the image's
         # cells only if the solver succeeds.  Off by default (it needs the cells on the host: one synchronisation per
         # step, which a replayed hipGraph cannot contain); cfg['RUNTIME']['TEACHER_PNP_GATE'] (--teacher_pnp_gate) turns
-        # it on for eager launches, with kd6d/libs/pnp.py as the solver
+        # it on: with the host solver for eager launches only, with PNP_SOLVER = "device" (kd6d_teacher_pnp_gate on the
+        # teacher's stream, no host round trip) in every launch mode
         self.teacher_pnp_gate = bool(cfg.get("RUNTIME", {}).get("TEACHER_PNP_GATE", False))
         self.loss_evaluator = KDLoss(cfg["INPUT"]["INTERNAL_K"], cfg["DATASETS"]["MESH_DIAMETERS"],
                                      cfg["SOLVER"]["FOCAL_GAMMA"], cfg["SOLVER"]["FOCAL_ALPHA"], self.positive_num,
@@ -199,7 +206,10 @@ class PoseModuleKD(nn.Module):
                                           self.positive_num, self.positive_lambda, frame_wh=tgt.frame_wh,
                                           flats=flats, zeroed=pre)
             if self.teacher_pnp_gate:
-                self._apply_pnp_gate(tk, cls, tgt)
+                if self.pnp_solver == "device":
+                    self._apply_pnp_gate_device(tk, cls, tgt)
+                else:
+                    self._apply_pnp_gate(tk, cls, tgt)
             return tk
         # evaluation: candidate cells per ground-truth class on the GPU, PnP-RANSAC on the host (models/model_kd.py:94-95)
         cls, reg = net.forward(x)
@@ -230,6 +240,22 @@ class PoseModuleKD(nn.Module):
                 ok = solve_pnp_ransac(xyz, uv, K[b], reproj_err=5.0)[0]
             keep.append(1 if ok else 0)
         tk.t_cnt.mul_(torch.tensor(keep, dtype=tk.t_cnt.dtype, device=tk.t_cnt.device))
+
+    PNP_GATE_ITERS = 300           # hypotheses per image (solve_pnp_ransac's default)
+    PNP_GATE_SEED = 0              # the same sampling every step: the gate is a function of the cells alone
+
+    def _apply_pnp_gate_device(self, tk, cls, tgt):
+        """_apply_pnp_gate on the device (kd6d_teacher_pnp_gate): same class pick, same solver structure, t_cnt
+        zeroed in place for the images without a pose.  No host copy, no synchronisation: capturable."""
+        B = tk.batch
+        ws = getattr(self, "_pnp_gate_ws", None)
+        need = int(ops.lib.kd6d_pnp_workspace_floats(B, self.PNP_GATE_ITERS))
+        if ws is None or ws.numel() < need or ws.device != tk.t_cnt.device:
+            ws = self._pnp_gate_ws = ops.pnp_workspace(B, self.PNP_GATE_ITERS, tk.t_cnt.device)
+        ops.teacher_pnp_gate(cls, self.net.n_cls, self.inference_th, tk.t_row, tk.t_cnt, tk.t_kp, tk.cap, tgt.kp3d,
+                             tgt.K, reproj_err=5.0, iters=self.PNP_GATE_ITERS, seed=self.PNP_GATE_SEED, workspace=ws)
+        for key in ("post_kp_2d", "post_kp_cls", "post_pos_per_img"):
+            tk.pop(key, None)
 
     def _begin_step(self, x):
         """Step prologue of the fused training step: ONE launch zeroes the gradient bucket (the reference's

@@ -605,6 +605,42 @@ def sinkhorn_div(xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, 
     return loss, valid, gx, ga
 
 
+def pnp_workspace(n_problems, iters, device):
+    """Scratch of kd6d_pnp_ransac / kd6d_teacher_pnp_gate (any contents): keep one per shape across calls."""
+    return torch.empty(max(int(lib.kd6d_pnp_workspace_floats(n_problems, iters)), 1), dtype=torch.float32, device=device)
+
+
+def pnp_ransac(kp, cnt, box, K, reproj_err=5.0, iters=300, seed=0, workspace=None):
+    """Batched PnP-RANSAC (csrc/pnp.hip).  kp (P*cap, 8, 2) px, cnt (P,) int32 cells per problem, box (P, 8, 3),
+    K (P, 3, 3).  -> ok (P,) int32, R (P, 3, 3), T (P, 3), n_inliers (P,) int32 (device tensors, no synchronisation)."""
+    P = cnt.numel()
+    cap = kp.shape[0] // max(P, 1)
+    dev = kp.device
+    if workspace is None:
+        workspace = pnp_workspace(P, iters, dev)
+    ok = torch.empty(P, dtype=torch.int32, device=dev)
+    n_inl = torch.empty(P, dtype=torch.int32, device=dev)
+    R = torch.empty(P, 3, 3, dtype=torch.float32, device=dev)
+    T = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    check(lib.kd6d_pnp_ransac(P, cap, _ptr(cnt), _ptr(kp), _ptr(box), _ptr(K), float(reproj_err), int(iters), int(seed),
+                              _ptr(ok), _ptr(R), _ptr(T), _ptr(n_inl), _ptr(workspace), workspace.numel(), _stream()),
+          "kd6d_pnp_ransac")
+    return ok, R, T, n_inl
+
+
+def teacher_pnp_gate(cls, n_cls, threshold, t_row, t_cnt, t_kp, cap, kp3d, K, reproj_err=5.0, iters=300, seed=0,
+                     workspace=None):
+    """In place on t_cnt (kd6d_teacher_select's slot arrays): images whose pose cannot be solved lose their cells.
+    kp3d (B, n_class_rows, 8, 3), K (B, 3, 3); no synchronisation (capturable)."""
+    B = t_cnt.numel()
+    if workspace is None:
+        workspace = pnp_workspace(B, iters, t_cnt.device)
+    check(lib.kd6d_teacher_pnp_gate(_ptr(cls), int(n_cls), float(threshold), _ptr(t_row), _ptr(t_cnt), _ptr(t_kp), cap,
+                                    B, _ptr(kp3d), int(kp3d.shape[1]), _ptr(K), float(reproj_err), int(iters),
+                                    int(seed), _ptr(workspace), workspace.numel(), _stream()),
+          "kd6d_teacher_pnp_gate")
+
+
 def sinkhorn_dense(x, alpha, y, beta, blur=0.05, scaling=0.5, reach=0.5, diameter=None, p=2.0):
     """Debiased (unbalanced) Sinkhorn divergence between two LARGE weighted point sets: x (N,D), alpha (N),
     y (M,D), beta (M), D in {2,4,8,16} -- losses/kd_loss.py:26-30 / loss_libs.py:47 with a dense grid of local
