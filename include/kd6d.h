@@ -467,6 +467,12 @@ int kd6d_sinkhorn_max_points(void);
  * kd6d_ssc_assign      <- losses/loss.py:164-268; per-image inputs are padded to KD6D_MAX_GT
  *   instances; keys (rows) are caller-supplied uniform randoms (the n smallest in-mask keys per
  *   level are the reference's randperm(...)[:n]).  labels (rows): -1 ignore, 0 bg, c+1.
+ *   Capacity: image b's positives are pos_row / pos_gt [b*cap, b*cap + pos_cnt[b]), ascending packed row, cap <= 64.
+ *   An instance draws at most floor(positive_num + 0.5 * levels) cells (the per-level counts are rounded half up), so
+ *   cap >= KD6D_MAX_GT * floor(positive_num + 0.5 * levels) -- 48 at the reference's positive_num = 10 -- holds every
+ *   pick and the labels are the reference's.  Beyond it the result is TRUNCATED, not an error: the cap picks with the
+ *   smallest packed rows are kept, pos_cnt[b] = cap, and every other pick keeps the in-mask label -1 (ignore)
+ *   instead of c+1.  The Python host (kd6d.kd_losses.KDLoss) refuses configurations that could get there.
  * kd6d_focal_fwd/bwd   <- losses/loss.py:20-40 (sum reduction into *loss through loss_ws, see kd6d_scalar_ws; bwd
  *   writes ALL of dcls).
  * kd6d_student_points  <- losses/kd_loss.py:40-71,152: decoded full-frame keypoints of the

@@ -406,8 +406,15 @@ __global__ __launch_bounds__(kT) void ssc_assign_kernel(
         block_argmax(bv, bi, s_v, s_i);
         if (bi == 0x7fffffff) break;   // fewer in-mask cells than n_k
         if (threadIdx.x == 0) {
-          const int slot = s_total;
-          if (slot < 64) { s_sel_row[slot] = row0 + b * hw + bi; s_sel_gt[slot] = g; }
+          const int slot = s_total, row = row0 + b * hw + bi;
+          if (slot < 64) { s_sel_row[slot] = row; s_sel_gt[slot] = g; }
+          else {
+            // list full: keep the 64 smallest rows, so that what survives is a prefix of the row order the
+            // output is documented in (not whatever the level / instance loop happened to reach first)
+            int worst = 0;
+            for (int i = 1; i < 64; ++i) if (s_sel_row[i] > s_sel_row[worst]) worst = i;
+            if (row < s_sel_row[worst]) { s_sel_row[worst] = row; s_sel_gt[worst] = g; }
+          }
           s_total = slot + 1;
           s_nkey[lo + bi] = -INFINITY;
         }

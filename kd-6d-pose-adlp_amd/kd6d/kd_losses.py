@@ -15,8 +15,17 @@ from ._lib import Levels, check, lib
 
 ANCHOR_SIZES = [32, 64, 128, 256, 512]
 ANCHOR_STRIDES = [8, 16, 32, 64, 128]
-CAP = 32          # slots per image for positives / teacher cells (reference: ~10, POSITIVE_NUM)
+CAP = 32          # slots per image for teacher cells / pose candidates (one class: <= 12; the PnP kernels take <= 32)
 MAX_GT = _lib.MAX_GT
+
+
+def positives_bound(positive_num, n_levels=_lib.MAX_SEG, instances=MAX_GT):
+    """Most positive cells kd6d_ssc_assign can pick in one image: per instance the per-level shares of positive_num,
+    each rounded half up, i.e. at most floor(positive_num + 0.5 * levels) (include/kd6d.h, kd6d_ssc_assign)."""
+    return instances * int(float(positive_num) + 0.5 * n_levels)
+
+
+POS_CAP = positives_bound(10)      # 48: slots per image for the student's positives at the reference's POSITIVE_NUM
 
 
 def make_levels(batch, shapes, sizes=ANCHOR_SIZES, strides=ANCHOR_STRIDES):
@@ -256,7 +265,7 @@ class KDLoss:
     """Student-side losses of one step.  forward() launches; backward(weights) fills dcls/dreg."""
 
     def __init__(self, internal_K, diameters, gamma=2.0, alpha=0.25, positive_num=10, positive_lambda=1.0,
-                 kd_cfg=None, cap=CAP):
+                 kd_cfg=None, cap=None):
         K = np.asarray(internal_K, np.float64).reshape(3, 3)
         self.kinv = (ctypes.c_float * 9)(*np.linalg.inv(K).reshape(-1).astype(np.float32).tolist())
         self.diameters_host = [float(d) for d in diameters]
@@ -277,7 +286,15 @@ class KDLoss:
         self.detach = bool(kd_cfg.get("DETACH", False))
         if not self.weighted:
             raise NotImplementedError("unweighted OT (--weightedOT false) is not implemented on the HIP path")
-        self.cap = cap
+        # every pick of a full image (MAX_GT instances) must fit: beyond `cap` the kernel truncates, and labels,
+        # losses and gradients would silently differ from the reference's
+        need = positives_bound(self.positive_num)
+        self.cap = max(POS_CAP, need) if cap is None else int(cap)
+        if self.cap > 64 or self.cap < need:
+            raise ValueError("KDLoss: positive_num=%g can select %d cells in an image with %d instances; cap=%d %s"
+                             % (self.positive_num, need, MAX_GT, self.cap,
+                                "exceeds the 64 slots of kd6d_ssc_assign" if self.cap > 64 else
+                                "would truncate them (include/kd6d.h, kd6d_ssc_assign)"))
         self.ctx = None
         self._ws = {}
         self._keys = {}
