@@ -518,6 +518,21 @@ int kd6d_teacher_pnp_gate(const float* cls, int n_cls, float threshold, const in
                           const float* t_kp, int cap, int batch, const float* kp3d, int n_class_rows, const float* K,
                           float reproj_err, int iters, uint64_t seed, float* workspace, int64_t workspace_floats,
                           void* stream);
+/* ---- pose errors of evaluation on the device (csrc/pose_err.hip; added under ABI 11, a new symbol only):
+ * libs/utils.py::compute_pose_diff for n_problems (ground truth, prediction) pairs in ONE launch, one workgroup per
+ * problem.  Problem p scores vcnt[p] (1 ... max_v, max_v <= KD6D_POSE_ERR_MAX_V = the reference's subsample size)
+ * vertices of one mesh: verts[voff[p] + vidx[p*max_v + i]], or verts[voff[p] + i] when vidx == NULL.  Both sets are
+ * moved into the camera frame ((Rg, Tg) and (Rp, Tp), K per problem); sym[p] != 0 matches every ground-truth vertex
+ * with the predicted vertex at the smallest 3D distance (ties: the lowest index, as np.argmin), else vertex i with
+ * vertex i.  err[p] = {mean 3D distance, mean distance of the pinhole projections p / (p_z + 1e-8) through K} of the
+ * matched pairs; nn (optional, (P, max_v)) = position i' < vcnt[p] of the vertex matched to vertex i, -1 from
+ * vcnt[p] on.  Differences are formed as Rg m_i - Rp m_j + (Tg - Tp), in fp32.  No atomics, sums in a fixed order: a
+ * pure function of the problem's own inputs, bitwise reproducible.  The caller guarantees that every index lies
+ * inside the pool (kd6d.ops.pose_errors checks it); a vcnt outside 0 ... max_v is clamped, 0 gives err = {0, 0}. */
+#define KD6D_POSE_ERR_MAX_V 1000
+int kd6d_pose_errors(int n_problems, int max_v, const float* verts, const int32_t* voff, const int32_t* vcnt,
+                     const int32_t* vidx, const float* K, const float* Rg, const float* Tg, const float* Rp,
+                     const float* Tp, const int32_t* sym, float* err, int32_t* nn, void* stream);
 int kd6d_ssc_assign(const kd6d_levels* levels, const float* mask, int mask_h, int mask_w, const float* kp3d,
                     const float* K, const int32_t* class_ids, const int32_t* n_gt, const float* rot,
                     const float* trans, const float* bbox_trans, const float* keys, float positive_num,

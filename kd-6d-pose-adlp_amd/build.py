@@ -37,7 +37,9 @@ EXTRA_FLAGS = {"sinkhorn_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # augment.hip runs in the loader, beside the other network's convolutions in pipelined mode: same switch
                "augment.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # pnp.hip: the teacher PnP gate runs on the teacher's stream, beside the student's convolutions
-               "pnp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "pnp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # pose_err.hip: a non-MFMA unit like the ones above, same switch (validation runs between training steps)
+               "pose_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

@@ -62,6 +62,7 @@ class BnIn(ctypes.Structure):
 MAX_GT = 4
 AUG_MAX_ID = 16                      # KD6D_AUG_MAX_ID: mask ids kd6d_aug_mask_stats / _relabel take
 MAX_ZERO = 8
+POSE_ERR_MAX_V = 1000                # KD6D_POSE_ERR_MAX_V: vertices kd6d_pose_errors scores per problem
 
 
 class GnItem(ctypes.Structure):
@@ -149,6 +150,7 @@ SIGNATURES = {
     "kd6d_pnp_workspace_floats": [_I, _I],
     "kd6d_pnp_ransac": [_I, _I, _P, _P, _P, _P, _F, _I, ctypes.c_uint64, _P, _P, _P, _P, _P, _I64, _P],
     "kd6d_teacher_pnp_gate": [_P, _I, _F, _P, _P, _P, _I, _I, _P, _I, _P, _F, _I, ctypes.c_uint64, _P, _I64, _P],
+    "kd6d_pose_errors": [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "kd6d_ssc_assign": [_L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P],
     "kd6d_focal_fwd": [_P, _P, _I, _F, _F, _P, _P, _P],
     "kd6d_focal_bwd": [_I, _P, _P, _I, _F, _F, _P, _P, _P],

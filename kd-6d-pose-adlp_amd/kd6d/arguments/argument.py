@@ -1,4 +1,6 @@
-"""Derived configuration keys (the hard-coded layer of arguments/argument.py:51-104)."""
+"""Derived configuration keys (the hard-coded layer of arguments/argument.py:51-104) and the command line of the
+evaluation entry test.py (arguments/argument.py:6-48: get_argparser / get_args)."""
+import argparse
 
 _BACKBONES = {
     # name: (FEAT_CHANNELS, OUT_CHANNEL, VAL_FREQ)
@@ -30,3 +32,44 @@ def custom_cfg(cfg):
         cfg["SOLVER"].setdefault(k, v)
     cfg["DATASETS"].setdefault("SYMMETRY_TYPES", {})
     return cfg
+
+
+def get_argparser():
+    """The reference's options of arguments/argument.py:6-22 that evaluation reads, under their names and defaults, plus
+    the additive ones of this build (--synthetic, --precision, --pnp_solver, --eval_scorer, --image_size)."""
+    p = argparse.ArgumentParser()
+    p.add_argument("--local_rank", type=int, default=0)
+    p.add_argument("--config_file", type=str, default="./configs/ape.yaml")
+    p.add_argument("--num_workers", type=int, default=8)
+    p.add_argument("--working_dir", type=str, default="./outputs/")
+    p.add_argument("--test_file", type=str, default="")
+    p.add_argument("--weight_file", type=str, default="")
+    p.add_argument("--running_device", type=str, default="cuda")
+    p.add_argument("--backbone", type=str, default="darknet53")
+    # additive (this build)
+    p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--synthetic", action="store_true", help="seeded LINEMOD-shaped synthetic batches (no dataset)")
+    p.add_argument("--image_size", type=int, default=256, help="synthetic crop size")
+    p.add_argument("--pnp_solver", type=str, default="host", choices=["host", "device"],
+                   help="PnP-RANSAC of evaluation: host = numpy (kd6d/libs/pnp.py), device = HIP (csrc/pnp.hip)")
+    p.add_argument("--eval_scorer", type=str, default="host", choices=["host", "device"],
+                   help="pose errors of evaluation: host = float64 numpy, one object at a time "
+                        "(kd6d/libs/evaluate.py); device = HIP (csrc/pose_err.hip), every object in one launch")
+    return p
+
+
+def get_args(argv=None):
+    """-> cfg: the yaml (a `_BASE_` file honoured) with cfg['RUNTIME'] filled as arguments/argument.py:32-38 does
+    (LOCAL_RANK, CONFIG_FILE, NUM_WORKERS, WEIGHT_FILE, WORKING_DIR, RUNNING_DEVICE) plus this build's keys."""
+    from .argument_kd import load_yaml
+    args = get_argparser().parse_args(argv)
+    cfg = load_yaml(args.config_file)
+    cfg["RUNTIME"] = dict(LOCAL_RANK=args.local_rank, CONFIG_FILE=args.config_file, NUM_WORKERS=args.num_workers,
+                          WEIGHT_FILE=args.weight_file, WORKING_DIR=args.working_dir,
+                          RUNNING_DEVICE=args.running_device, PRECISION=args.precision, SYNTHETIC=bool(args.synthetic),
+                          IMAGE_SIZE=int(args.image_size), PNP_SOLVER=args.pnp_solver, EVAL_SCORER=args.eval_scorer)
+    if len(args.test_file) > 0:
+        cfg["DATASETS"]["TEST"] = args.test_file
+    cfg["DATASETS"].setdefault("MIXED_CLASSES", False)
+    cfg["MODEL"]["BACKBONE"] = args.backbone
+    return custom_cfg(cfg)

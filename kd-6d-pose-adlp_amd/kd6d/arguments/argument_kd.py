@@ -2,8 +2,8 @@
 
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
-overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver; yaml files may name
-a `_BASE_` file.
+overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer; yaml files
+may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -77,6 +77,9 @@ def get_argparser():
     p.add_argument("--pnp_solver", type=str, default="host", choices=["host", "device"],
                    help="PnP-RANSAC of the teacher gate and of evaluation: host = numpy (kd6d/libs/pnp.py), one call "
                         "per object; device = HIP (csrc/pnp.hip), a batch per launch, no host synchronisation")
+    p.add_argument("--eval_scorer", type=str, default="host", choices=["host", "device"],
+                   help="pose errors of validation: host = float64 numpy, one object at a time "
+                        "(kd6d/libs/evaluate.py); device = HIP (csrc/pose_err.hip), every object of a validation in one launch")
     p.add_argument("--two_launch_norm_bwd", action="store_true",
                    help="BatchNorm / GroupNorm backward as reduce + apply launches instead of one launch with an "
                         "in-kernel barrier (the remedy train_kd.py names when a barrier wait timed out)")
@@ -115,6 +118,7 @@ def _runtime(args, config_file, weight_file):
     return dict(LOCAL_RANK=args.local_rank, CONFIG_FILE=config_file, NUM_WORKERS=args.num_workers,
                 WEIGHT_FILE=weight_file, RUNNING_DEVICE=args.running_device, PRECISION=args.precision,
                 TEACHER_PNP_GATE=bool(args.teacher_pnp_gate), PNP_SOLVER=getattr(args, "pnp_solver", "host"),
+                EVAL_SCORER=getattr(args, "eval_scorer", "host"),
                 TWO_LAUNCH_NORM_BWD=bool(args.two_launch_norm_bwd), EXCHANGE=args.exchange,
                 RCCL_SINGLE_RANK=bool(getattr(args, "rccl_single_rank", False)))
 

@@ -11,7 +11,9 @@ import numpy as np
 import torch
 
 from .distributed import get_rank
-from .evaluate import evaluate_pose_predictions, remap_predictions
+from .evaluate import evaluate_pose_predictions, evaluate_pose_predictions_device, remap_predictions
+
+SCORERS = ("host", "device")
 
 
 class _Mesh:
@@ -20,9 +22,14 @@ class _Mesh:
 
 
 @torch.no_grad()
-def valid(cfg, steps, loader, model, device, meshes, logger=None):
+def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host", preds_out=None):
     """meshes: per class id an (n,3) vertex array (or an object with `.vertices`).  -> the 6-tuple of
-    evaluate_pose_predictions on rank 0, None elsewhere."""
+    evaluate_pose_predictions on rank 0, None elsewhere.
+    scorer: "host" scores object by object in float64 numpy (evaluate_pose_predictions); "device" scores every object of
+    the run in one kd6d_pose_errors launch (evaluate_pose_predictions_device).  preds_out: a dict that receives the
+    collected {path: {'meta', 'pred'}} entries (what the reference's valid() writes to preds.json)."""
+    if scorer not in SCORERS:
+        raise ValueError("valid(): scorer=%r (one of %s)" % (scorer, ", ".join(SCORERS)))
     was_training = model.training
     model.eval()
     preds = {}
@@ -41,11 +48,17 @@ def valid(cfg, steps, loader, model, device, meshes, logger=None):
             best = [list(p[0][:-1])] if len(p) else []
             preds[m["path"]] = {"meta": m, "pred": best}
     model.train(was_training)
+    if preds_out is not None:
+        preds_out.update(preds)
     if get_rank() != 0:
         return None
     ms = [m if hasattr(m, "vertices") else _Mesh(m) for m in meshes]
-    out = evaluate_pose_predictions(preds, cfg["DATASETS"]["N_CLASS"], ms, cfg["DATASETS"]["MESH_DIAMETERS"],
-                                    cfg["DATASETS"].get("SYMMETRY_TYPES", {}))
+    if scorer == "device":
+        out = evaluate_pose_predictions_device(preds, cfg["DATASETS"]["N_CLASS"], ms, cfg["DATASETS"]["MESH_DIAMETERS"],
+                                               cfg["DATASETS"].get("SYMMETRY_TYPES", {}), device)
+    else:
+        out = evaluate_pose_predictions(preds, cfg["DATASETS"]["N_CLASS"], ms, cfg["DATASETS"]["MESH_DIAMETERS"],
+                                        cfg["DATASETS"].get("SYMMETRY_TYPES", {}))
     if logger is not None:            # eval_libs.py:112-146 of the reference: per class, then the mean over classes seen
         all_adi, all_rep, n_valid = {}, {}, 0
         for i, (adi, rep) in enumerate(zip(out[0], out[2])):

@@ -237,6 +237,21 @@ def build_dataset(cfg, device="cuda", augment=False):
             DziLoader(loader(valid_set, False), cfg, device, False))
 
 
+def build_test_dataset(cfg, device="cuda"):
+    """test.py:74-134 of the reference: the valid-style loader (no shuffle, no augmentation, DZI crop) over the image
+    list(s) of DATASETS.TEST, for one process."""
+    from torch.utils.data import ConcatDataset, DataLoader
+    from .dataset import BOP_Dataset, collate_frames
+    ds = cfg["DATASETS"]
+    files = [ds["TEST"]] if isinstance(ds["TEST"], str) else list(ds["TEST"])
+    sets = [BOP_Dataset(f, ds["MESH_DIR"], ds["BBOX_FILE"], ds.get("SYMMETRY_TYPES"), training=False) for f in files]
+    dset = sets[0] if len(sets) == 1 else ConcatDataset(sets)
+    per_gpu = int(cfg.get("TEST", {}).get("IMS_PER_BATCH", cfg["SOLVER"]["IMS_PER_BATCH"]))
+    loader = DataLoader(dset, batch_size=per_gpu, sampler=torch.utils.data.SequentialSampler(dset),
+                        num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0), collate_fn=collate_frames)
+    return DziLoader(loader, cfg, device, False)
+
+
 def dataset_meshes(loader):
     """Mesh vertex arrays per class id of a DziLoader's dataset (what valid() measures ADI / REP on)."""
     dset = loader.loader.dataset

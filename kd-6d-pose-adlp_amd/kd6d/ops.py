@@ -641,6 +641,49 @@ def teacher_pnp_gate(cls, n_cls, threshold, t_row, t_cnt, t_kp, cap, kp3d, K, re
           "kd6d_teacher_pnp_gate")
 
 
+def pose_errors(verts, voff, vcnt, vidx, K, Rg, Tg, Rp, Tp, sym, max_v=None, want_nn=False, validate=True):
+    """Mean 3D / 2D-reprojection error of P (ground truth, prediction) pairs in one launch (csrc/pose_err.hip,
+    evaluate.py::compute_pose_diff).  verts (Nv, 3) fp32 pool; voff, vcnt, sym (P,) int32; vidx (P, max_v) int32 relative
+    to voff, or None (vertices 0 ... vcnt-1; max_v then has to be given); K, Rg, Rp (P, 3, 3), Tg, Tp (P, 3) fp32.
+    -> err (P, 2) [, nn (P, max_v) int32] (device tensors, no synchronisation).
+    validate: check on the device that every index stays inside the pool and read the verdict back (ONE
+    synchronisation; the kernel itself cannot know the pool's size).  Callers that built the index arrays themselves and
+    replay the launch in a captured graph pass False."""
+    P = voff.numel()
+    dev = verts.device
+    if vidx is not None:
+        assert vidx.dtype == torch.int32 and vidx.dim() == 2 and vidx.shape[0] == P
+        max_v = vidx.shape[1] if max_v is None else max_v
+        assert vidx.shape[1] == max_v
+    assert max_v is not None, "pose_errors: max_v is needed without an index table"
+    assert verts.dtype == torch.float32 and verts.dim() == 2 and verts.shape[1] == 3
+    for t in (voff, vcnt, sym):
+        assert t.dtype == torch.int32 and t.numel() == P
+    for t, n in ((K, 9), (Rg, 9), (Rp, 9), (Tg, 3), (Tp, 3)):
+        assert t.dtype == torch.float32 and t.numel() == P * n
+    if validate and P > 0:
+        Nv = verts.shape[0]
+        cnt = vcnt.long()
+        bad = (voff < 0) | (cnt < 1) | (cnt > max_v)
+        if vidx is None:
+            bad = bad | (voff.long() + cnt > Nv)
+        else:
+            used = torch.arange(max_v, device=dev)[None, :] < cnt[:, None]
+            at = voff.long()[:, None] + vidx.long()
+            bad = bad | (used & ((vidx < 0) | (at >= Nv))).any(dim=1)
+        if bool(bad.any()):
+            raise ValueError("pose_errors: problem %d points outside the vertex pool of %d vertices (or its vcnt is "
+                             "outside 1 ... %d)" % (int(torch.nonzero(bad)[0]), Nv, max_v))
+    err = torch.empty(P, 2, dtype=torch.float32, device=dev)
+    nn = torch.empty(P, max_v, dtype=torch.int32, device=dev) if want_nn else None
+    if P == 0:
+        return (err, nn) if want_nn else err
+    check(lib.kd6d_pose_errors(P, int(max_v), _ptr(verts), _ptr(voff), _ptr(vcnt), _ptr(vidx), _ptr(K), _ptr(Rg),
+                               _ptr(Tg), _ptr(Rp), _ptr(Tp), _ptr(sym), _ptr(err), _ptr(nn), _stream()),
+          "kd6d_pose_errors")
+    return (err, nn) if want_nn else err
+
+
 def sinkhorn_dense(x, alpha, y, beta, blur=0.05, scaling=0.5, reach=0.5, diameter=None, p=2.0):
     """Debiased (unbalanced) Sinkhorn divergence between two LARGE weighted point sets: x (N,D), alpha (N),
     y (M,D), beta (M), D in {2,4,8,16} -- losses/kd_loss.py:26-30 / loss_libs.py:47 with a dense grid of local

@@ -1,0 +1,96 @@
+"""Evaluation entry point -- the reference's test.py:32-137 on the MI355X-native kd6d path: score a saved
+checkpoint without starting a training run.
+
+    python test.py --config_file ./configs/ape.yaml --backbone darknet_tiny_h --weight_file outputs/ape/kd/final.pth \
+        --working_dir outputs/ape/test/ --pnp_solver device --eval_scorer device [--test_file list.txt | --synthetic]
+
+Builds the network named by --backbone, loads --weight_file (a bare state dict or one under a 'model' key, loosely by
+name as the reference does; says whether weights were loaded or are random), builds the valid-style loader over
+DATASETS.TEST (--test_file overrides it; --synthetic: the seeded held-out batches train_kd.py validates on) and runs
+kd6d.libs.eval_libs.valid().  Writes, under --working_dir,
+    preds.json    per image: meta plus the best prediction [score, class, R, T], numpy converted to lists (what the
+                  reference's valid() writes, eval_libs.py:96-100)
+    metrics.json  the six values valid() returns: per-class ADI / AUC / REP accuracies, ADI / REP per depth bin and
+                  the depth range
+and prints the per-class ADI / AUC / REP table (utils.py:620-653).
+
+One process: rank 0 evaluates, as valid() does; the reference's multi-process gather of predictions
+(libs/train_libs.py accumulate_dicts) is not rebuilt.
+"""
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "kd-6d-pose-adlp_amd"))
+
+import numpy as np  # noqa: E402
+
+
+def print_accuracy_per_class(adi_per_class, auc_per_class, rep_per_class):
+    """utils.py:620-653: one title line, then one line per class that was seen."""
+    assert len(adi_per_class) == len(rep_per_class)
+    first = True
+    for c, (adi, auc, rep) in enumerate(zip(adi_per_class, auc_per_class, rep_per_class)):
+        if len(adi) == 0:
+            continue
+        if first:
+            print("\t" + "".join(k + " " for k in list(adi) + list(auc) + list(rep)))
+            first = False
+        print("cls_%02d" % c + "".join("\t%.2f" % v for v in list(adi.values()) + list(auc.values()) + list(rep.values())))
+
+
+def _jsonable(x):
+    if isinstance(x, dict):
+        return {str(k): _jsonable(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_jsonable(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    if isinstance(x, np.generic):
+        return x.item()
+    if hasattr(x, "detach"):
+        return x.detach().cpu().tolist()
+    return x
+
+
+def main(argv=None):
+    from kd6d.arguments.argument import get_args
+    cfg = get_args(argv)
+    device = cfg["RUNTIME"]["RUNNING_DEVICE"]
+    if device != "cuda":
+        raise SystemExit("the kd6d step runs on MI355X only (--running_device cuda); the CPU restatement "
+                         "lives in oracle/ and is test infrastructure")
+    import torch
+    from kd6d.libs.eval_libs import valid
+    from kd6d.libs.train_libs import build_model_teacher, build_test_dataset, dataset_meshes
+    from kd6d.models.model_kd import PoseModuleKD as PoseModule
+    torch.manual_seed(0)
+    np.random.seed(0)
+    cfg["RUNTIME"].update(N_GPU=1, DISTRIBUTED=False)
+    torch.cuda.set_device(int(cfg["RUNTIME"]["LOCAL_RANK"]))
+    wd = cfg["RUNTIME"]["WORKING_DIR"]
+    print("working directory: " + wd)
+    os.makedirs(wd, exist_ok=True)
+
+    model = build_model_teacher(cfg, PoseModule, device)      # builds the backbone, loads WEIGHT_FILE loosely, says which
+    if cfg["RUNTIME"]["SYNTHETIC"]:
+        from train_kd import synthetic_valid_loader
+        loader, meshes = synthetic_valid_loader(cfg, device)
+    else:
+        loader = build_test_dataset(cfg, device)
+        meshes = dataset_meshes(loader)
+
+    preds = {}
+    out = valid(cfg, 0, loader, model, device, meshes, scorer=cfg["RUNTIME"]["EVAL_SCORER"], preds_out=preds)
+    with open(os.path.join(wd, "preds.json"), "w") as f:
+        json.dump(_jsonable(preds), f)
+    names = ("adi_per_class", "auc_per_class", "rep_per_class", "adi_per_depth", "rep_per_depth", "depth_range")
+    with open(os.path.join(wd, "metrics.json"), "w") as f:
+        json.dump(_jsonable(dict(zip(names, out))), f, indent=1)
+    print("%d images scored (%s scorer, %s PnP)" % (len(preds), cfg["RUNTIME"]["EVAL_SCORER"], cfg["RUNTIME"]["PNP_SOLVER"]))
+    print_accuracy_per_class(out[0], out[1], out[2])
+
+
+if __name__ == "__main__":
+    main()

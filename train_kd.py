@@ -12,8 +12,8 @@ Dynamic-Zoom-In crop + normalisation run on the GPU; --augment adds the referenc
 INTERNAL_K included, on the GPU front-end); with it, seeded LINEMOD-shaped batches.  As in the
 reference the teacher is validated once before training (skip with --skip_teacher_eval) and every VAL_FREQ steps
 rank 0 validates the student (kd6d/libs/eval_libs.valid: eval forward -> pose candidates -> PnP-RANSAC -> ADI /
-REP) and writes latest.pth.  Scalars go to tensorboardX under the reference's tags when that package is
-installed, else to <working_dir>/scalars.jsonl with the same tags.
+REP; --eval_scorer device scores the poses in one launch) and writes latest.pth; test.py scores a saved checkpoint.
+Scalars go to tensorboardX under the reference's tags when that package is installed, else to <working_dir>/scalars.jsonl with the same tags.
 """
 import json
 import os
@@ -177,10 +177,11 @@ if __name__ == "__main__":
             json.dump(cfg, f, indent=4, sort_keys=True, default=str)
     logger = ScalarWriter(wd) if get_rank() == 0 else None
 
+    scorer = cfg["RUNTIME"].get("EVAL_SCORER", "host")        # --eval_scorer: pose errors on the host or in one launch
     model_t.eval()
     if get_rank() == 0 and not cfg["RUNTIME"]["SKIP_TEACHER_EVAL"]:
         # train_kd.py:85-86 of the reference: the teacher's own accuracy before distilling from it
-        acc_t = valid(cfg_t, 0, valid_loader, model_t, device, valid_meshes)
+        acc_t = valid(cfg_t, 0, valid_loader, model_t, device, valid_meshes, scorer=scorer)
         seen = [a for a in acc_t[0] if a]
         print("teacher valid: %s" % ({k: round(float(sum(a[k] for a in seen)) / len(seen), 2) for k in seen[0]}
                                       if seen else "no objects"))
@@ -220,7 +221,8 @@ if __name__ == "__main__":
     for idx, (images, targets, _) in enumerate(train_loader):
         if total_steps >= MAX_ITER:
             if get_rank() == 0:
-                valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger)      # train_kd.py:95-99
+                valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger,      # train_kd.py:95-99
+                      scorer=scorer)
                 torch.save(model.state_dict(), os.path.join(wd, "final.pth"))
             print("Training finished")
             break
@@ -271,7 +273,8 @@ if __name__ == "__main__":
             # leave the others waiting in the next gradient all-reduce.
             stop_if_barrier_timeouts(lib.kd6d_barrier_timeouts(), cfg["RUNTIME"]["DISTRIBUTED"])
         if get_rank() == 0 and total_steps % VAL_FREQ == 0:
-            acc = valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger)     # train_kd.py:148-150
+            acc = valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger,     # train_kd.py:148-150
+                        scorer=scorer)
             model.train()
             seen = [a for a in acc[0] if a]
             print("valid @ %d: %s" % (total_steps, {k: round(float(sum(a[k] for a in seen)) / len(seen), 2) for k in seen[0]}
