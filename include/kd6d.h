@@ -558,6 +558,36 @@ int kd6d_loss_backward(const kd6d_levels* levels, int dtype, const float* cls, c
                        int64_t* dseg_scale_acc, int64_t acc_hi_stride, float frame_w, float frame_h, int cap,
                        int detach_alpha, void* dcls, void* dreg, void* stream);
 
+/* ---- per-object KD (added under ABI 11, new symbols only): one OT problem per (image, ground-truth slot) instead of
+ * one per image.  Object o = b*KD6D_MAX_GT + g exists for g < n_gt[b].
+ * kd6d_teacher_select_objects: kd6d_pose_candidates' selection (the kd6d_teacher_select rule restricted to class
+ *   class_ids[b*KD6D_MAX_GT + g]) with kd6d_teacher_select's full outputs: object o owns slots
+ *   [o*cap, o*cap + t_cnt[o]) of t_kp / t_score / t_row / t_kp_norm / t_beta; t_cnt[o] = 0 for g >= n_gt[b].  t_kp and
+ *   t_score are bitwise kd6d_pose_candidates' kp and score.  Two slots of one image with the same class get the same
+ *   cells (the teacher cannot tell instances of one class apart).
+ * kd6d_kd_group_objects: stable partition of image b's positive slots [b*cap, b*cap + pos_cnt[b]) (cap <= 64) by
+ *   pos_gt.  obj_start[o] / obj_cnt[o]: object o's segment of the object-major arrays, inside the image's own block
+ *   and in ascending slot (= packed row) order; dest[b*cap + i] = where slot i went; xs_obj (slots,8,2) / alpha_obj
+ *   (slots,8) = bit copies of xs / alpha in that order.  A slot whose pos_gt is outside 0..KD6D_MAX_GT-1 goes behind
+ *   the last object and belongs to none.  Slots from pos_cnt[b] on are not written.
+ * kd6d_kd_scatter_objects: grad_xs[slot] = grad_xs_obj[dest[slot]] (grad_alpha alike) for the cells of an object with
+ *   valid_obj[o] > 0, zeros for every other positive slot; valid_img[b] = 1 when image b has a valid object, else 0.
+ * The step: kd6d_student_points -> kd6d_kd_group_objects -> kd6d_sinkhorn_div_fwd_bwd over batch*KD6D_MAX_GT problems
+ * (student segments obj_start / obj_cnt, teacher segments o*cap / t_cnt) -> kd6d_kd_mean over the same count ->
+ * kd6d_kd_scatter_objects -> kd6d_loss_backward with valid_img and n_valid = the number of valid objects.
+ * No atomics; every output is a function of the image's own rows: two launches agree bitwise. */
+int kd6d_teacher_select_objects(const kd6d_levels* levels, const float* cls, const float* reg,
+                                const float* bbox_trans, const int32_t* class_ids, const int32_t* n_gt,
+                                float threshold, float positive_num, float positive_lambda, int cap, float frame_w,
+                                float frame_h, int32_t* t_cnt, float* t_kp, float* t_score, int32_t* t_row,
+                                float* t_kp_norm, float* t_beta, void* stream);
+int kd6d_kd_group_objects(const int32_t* pos_cnt, const int32_t* pos_gt, const float* xs, const float* alpha,
+                          int batch, int cap, int32_t* obj_start, int32_t* obj_cnt, int32_t* dest, float* xs_obj,
+                          float* alpha_obj, void* stream);
+int kd6d_kd_scatter_objects(const int32_t* pos_cnt, const int32_t* pos_gt, const int32_t* dest,
+                            const int32_t* valid_obj, const float* grad_xs_obj, const float* grad_alpha_obj,
+                            int batch, int cap, float* grad_xs, float* grad_alpha, int32_t* valid_img, void* stream);
+
 /* ---- dense optimal transport (BASELINE config 5: D-dimensional local predictions over a whole cell grid,
  * thousands of points per set; the reference would need geomloss' KeOps backend above 5000^2 pairs).  Same
  * divergence and gradients as kd6d_sinkhorn_div_fwd_bwd for ONE problem: x (N,D) with weights alpha (N)

@@ -667,6 +667,84 @@ __global__ __launch_bounds__(kT) void loss_backward_kernel(Levels L, BackwardArg
   }
 }
 
+// ------------------------------------------------------------------------------------
+// Per-object KD (kd6d_kd_group_objects / kd6d_kd_scatter_objects): the OT problem of image b, ground-truth slot g
+// is object o = b*kMaxGt + g.  One wave64 per image; lane = positive slot (cap <= 64).
+// ------------------------------------------------------------------------------------
+// Stable partition of image b's positive slots by pos_gt: object g's cells, in ascending slot (= packed row) order,
+// move to [obj_start[o], obj_start[o] + obj_cnt[o]) of the object-major copies xs_obj / alpha_obj; dest[b*cap + slot]
+// is where slot went.  Slots whose pos_gt is outside 0..kMaxGt-1 follow the last object and belong to none.
+__global__ __launch_bounds__(64) void kd_group_objects_kernel(
+    const int* __restrict__ pos_cnt, const int* __restrict__ pos_gt, const float* __restrict__ xs,
+    const float* __restrict__ alpha, int cap, int* __restrict__ obj_start, int* __restrict__ obj_cnt,
+    int* __restrict__ dest, float* __restrict__ xs_obj, float* __restrict__ alpha_obj) {
+  __shared__ int s_dest[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int n = pos_cnt[b];
+  n = n < 0 ? 0 : (n > cap ? cap : n);
+  const int g = lane < n ? pos_gt[b * cap + lane] : -1;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int base = 0, mine = -1;
+#pragma unroll
+  for (int q = 0; q <= kMaxGt; ++q) {      // q == kMaxGt: the slots of no object
+    const bool in = q < kMaxGt ? g == q : (lane < n && (g < 0 || g >= kMaxGt));
+    const unsigned long long m = __ballot(in);
+    if (in) mine = base + __popcll(m & below);
+    if (q < kMaxGt && lane == 0) {
+      obj_start[b * kMaxGt + q] = b * cap + base;
+      obj_cnt[b * kMaxGt + q] = __popcll(m);
+    }
+    base += __popcll(m);
+  }
+  s_dest[lane] = mine;
+  if (lane < n) dest[b * cap + lane] = b * cap + mine;
+  __syncthreads();
+  for (int e = lane; e < n * 16; e += 64) {
+    const int slot = e >> 4, i = e & 15;
+    xs_obj[(size_t)(b * cap + s_dest[slot]) * 16 + i] = xs[(size_t)(b * cap + slot) * 16 + i];
+  }
+  for (int e = lane; e < n * 8; e += 64) {
+    const int slot = e >> 3, i = e & 7;
+    alpha_obj[(size_t)(b * cap + s_dest[slot]) * 8 + i] = alpha[(size_t)(b * cap + slot) * 8 + i];
+  }
+}
+
+// The way back: grad_xs / grad_alpha of the object-major problems into slot order, zeros for the cells of an object
+// without a valid problem (valid_obj <= 0) or of no object; valid_img[b] = 1 when image b holds a valid object.
+__global__ __launch_bounds__(64) void kd_scatter_objects_kernel(
+    const int* __restrict__ pos_cnt, const int* __restrict__ pos_gt, const int* __restrict__ dest,
+    const int* __restrict__ valid_obj, const float* __restrict__ g_xs_obj, const float* __restrict__ g_alpha_obj,
+    int cap, float* __restrict__ g_xs, float* __restrict__ g_alpha, int* __restrict__ valid_img) {
+  __shared__ int s_src[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int n = pos_cnt[b];
+  n = n < 0 ? 0 : (n > cap ? cap : n);
+  int src = -1;
+  if (lane < n) {
+    const int g = pos_gt[b * cap + lane];
+    const int d = dest[b * cap + lane];
+    if (g >= 0 && g < kMaxGt && valid_obj[b * kMaxGt + g] > 0 && d >= b * cap && d < b * cap + cap) src = d;
+  }
+  s_src[lane] = src;
+  if (lane == 0) {
+    int any = 0;
+#pragma unroll
+    for (int q = 0; q < kMaxGt; ++q) any |= valid_obj[b * kMaxGt + q] > 0;
+    valid_img[b] = any;
+  }
+  __syncthreads();
+  for (int e = lane; e < n * 16; e += 64) {
+    const int slot = e >> 4, i = e & 15;
+    const int s = s_src[slot];
+    g_xs[(size_t)(b * cap + slot) * 16 + i] = s >= 0 ? g_xs_obj[(size_t)s * 16 + i] : 0.f;
+  }
+  for (int e = lane; e < n * 8; e += 64) {
+    const int slot = e >> 3, i = e & 7;
+    const int s = s_src[slot];
+    g_alpha[(size_t)(b * cap + slot) * 8 + i] = s >= 0 ? g_alpha_obj[(size_t)s * 8 + i] : 0.f;
+  }
+}
+
 bool fill_levels(const kd6d_levels* lv, Levels* L) {
   if (!lv || lv->n < 1 || lv->n > KD6D_MAX_SEG || lv->batch < 1) return false;
   memset(L, 0, sizeof(*L));
@@ -730,6 +808,55 @@ extern "C" int kd6d_pose_candidates(const kd6d_levels* levels, const float* cls,
                      cls, reg, L, bbox_trans, threshold, positive_num, positive_lambda, cap, 1.f, 1.f,
                      cnt, kp, score, (int*)nullptr, (float*)nullptr, (float*)nullptr, class_ids, n_gt);
   KD6D_CHECK_LAUNCH("kd6d_pose_candidates");
+  return KD6D_OK;
+}
+
+extern "C" int kd6d_teacher_select_objects(const kd6d_levels* levels, const float* cls, const float* reg,
+                                           const float* bbox_trans, const int32_t* class_ids, const int32_t* n_gt,
+                                           float threshold, float positive_num, float positive_lambda, int cap,
+                                           float frame_w, float frame_h, int32_t* t_cnt, float* t_kp, float* t_score,
+                                           int32_t* t_row, float* t_kp_norm, float* t_beta, void* stream) {
+  Levels L;
+  KD6D_CHECK_ARG(fill_levels(levels, &L), "kd6d_teacher_select_objects: bad level table");
+  KD6D_CHECK_ARG(cls && reg && bbox_trans && class_ids && n_gt && t_cnt && t_kp && t_score && t_row && t_kp_norm &&
+                     t_beta && cap > 0 && cap <= 64 && frame_w > 0.f && frame_h > 0.f,
+                 "kd6d_teacher_select_objects: bad arguments (cap must be in 1..64)");
+  KD6D_CHECK_ARG(threshold > 0.f && threshold < 1.f, "kd6d_teacher_select_objects: threshold must be in (0,1)");
+  KD6D_CHECK_ARG(total_cells(L) * sizeof(float) <= 60 * 1024,
+                 "kd6d_teacher_select_objects: %zu cells per image exceed the LDS table", total_cells(L));
+  hipLaunchKernelGGL(teacher_select_kernel, dim3(L.batch, KD6D_MAX_GT), dim3(kT), total_cells(L) * sizeof(float),
+                     reinterpret_cast<hipStream_t>(stream),
+                     cls, reg, L, bbox_trans, threshold, positive_num, positive_lambda, cap, frame_w, frame_h,
+                     t_cnt, t_kp, t_score, t_row, t_kp_norm, t_beta, class_ids, n_gt);
+  KD6D_CHECK_LAUNCH("kd6d_teacher_select_objects");
+  return KD6D_OK;
+}
+
+extern "C" int kd6d_kd_group_objects(const int32_t* pos_cnt, const int32_t* pos_gt, const float* xs,
+                                     const float* alpha, int batch, int cap, int32_t* obj_start, int32_t* obj_cnt,
+                                     int32_t* dest, float* xs_obj, float* alpha_obj, void* stream) {
+  KD6D_CHECK_ARG(pos_cnt && pos_gt && xs && alpha && obj_start && obj_cnt && dest && xs_obj && alpha_obj,
+                 "kd6d_kd_group_objects: null pointer");
+  KD6D_CHECK_ARG(batch > 0 && cap > 0 && cap <= 64, "kd6d_kd_group_objects: bad arguments (batch=%d, cap=%d must be in 1..64)",
+                 batch, cap);
+  hipLaunchKernelGGL(kd_group_objects_kernel, dim3(batch), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     pos_cnt, pos_gt, xs, alpha, cap, obj_start, obj_cnt, dest, xs_obj, alpha_obj);
+  KD6D_CHECK_LAUNCH("kd6d_kd_group_objects");
+  return KD6D_OK;
+}
+
+extern "C" int kd6d_kd_scatter_objects(const int32_t* pos_cnt, const int32_t* pos_gt, const int32_t* dest,
+                                       const int32_t* valid_obj, const float* grad_xs_obj,
+                                       const float* grad_alpha_obj, int batch, int cap, float* grad_xs,
+                                       float* grad_alpha, int32_t* valid_img, void* stream) {
+  KD6D_CHECK_ARG(pos_cnt && pos_gt && dest && valid_obj && grad_xs_obj && grad_alpha_obj && grad_xs && grad_alpha &&
+                     valid_img,
+                 "kd6d_kd_scatter_objects: null pointer");
+  KD6D_CHECK_ARG(batch > 0 && cap > 0 && cap <= 64, "kd6d_kd_scatter_objects: bad arguments (batch=%d, cap=%d must be in 1..64)",
+                 batch, cap);
+  hipLaunchKernelGGL(kd_scatter_objects_kernel, dim3(batch), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                     pos_cnt, pos_gt, dest, valid_obj, grad_xs_obj, grad_alpha_obj, cap, grad_xs, grad_alpha, valid_img);
+  KD6D_CHECK_LAUNCH("kd6d_kd_scatter_objects");
   return KD6D_OK;
 }
 

@@ -159,6 +159,9 @@ SIGNATURES = {
     "kd6d_kd_mean": [_P, _P, _I, _P, _P, _P],
     "kd6d_loss_backward": [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _F, _F, _I, _I,
                            _P, _P, _P],
+    "kd6d_teacher_select_objects": [_L, _P, _P, _P, _P, _P, _F, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P],
+    "kd6d_kd_group_objects": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "kd6d_kd_scatter_objects": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kd6d_dzi_crop": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P],
     "kd6d_aug_warp_u8": [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P],
     "kd6d_aug_mask_stats": [_P, _I, _I, _I, _I, _P, _P],

@@ -2,8 +2,8 @@
 
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
-overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer; yaml files
-may name a `_BASE_` file.
+overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
+--synthetic_instances; yaml files may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -91,6 +91,12 @@ def get_argparser():
                         "communicator, the parameter broadcast and every step's all-reduce (rehearsal on a one-GPU box)")
     p.add_argument("--mixed_classes", type=str2bool, nargs="?", const=True, default=None,
                    help="synthetic batches mix the 13 LINEMOD classes (default: DATASETS.MIXED_CLASSES of the yaml)")
+    p.add_argument("--kd_per_object", action="store_true",
+                   help="distil per object: one OT problem per (image, ground-truth instance) -- the instance's positives "
+                        "against the teacher's cells of its class -- instead of one per image (the reference's rule, "
+                        "correct for one object per image only).  Not with --teacher_pnp_gate")
+    p.add_argument("--synthetic_instances", type=int, default=1, choices=[1, 2, 3, 4],
+                   help="--synthetic: objects of distinct classes per image (masks in vertical strips)")
     return p
 
 
@@ -124,6 +130,9 @@ def _runtime(args, config_file, weight_file):
 
 
 def build_cfgs(args):
+    if getattr(args, "kd_per_object", False) and args.teacher_pnp_gate:
+        from ..kd_losses import PER_OBJECT_GATE_ERROR
+        raise SystemExit(PER_OBJECT_GATE_ERROR)
     cfg = load_yaml(args.config_file)
     cfg["RUNTIME"] = _runtime(args, args.config_file, args.weight_file)
     cfg["RUNTIME"]["WORKING_DIR"] = args.working_dir
@@ -133,6 +142,7 @@ def build_cfgs(args):
     cfg["RUNTIME"]["LAUNCH"] = args.launch
     cfg["RUNTIME"]["TEACHER_GROUP"] = max(1, int(args.teacher_group))
     cfg["RUNTIME"]["IMAGE_SIZE"] = int(args.image_size)
+    cfg["RUNTIME"]["SYNTHETIC_INSTANCES"] = int(getattr(args, "synthetic_instances", 1))
     if args.mixed_classes is not None:
         cfg["DATASETS"]["MIXED_CLASSES"] = bool(args.mixed_classes)
     cfg["DATASETS"].setdefault("MIXED_CLASSES", False)
@@ -157,6 +167,9 @@ def build_cfgs(args):
     cfg_t["MODEL"]["BACKBONE"] = args.backbone_t
     cfg_t = custom_cfg(cfg_t)
     cfg_t.setdefault("KD", {})
+    if getattr(args, "kd_per_object", False):      # both modules read it: the teacher selects, the student solves per object
+        cfg["KD"]["PER_OBJECT"] = True
+        cfg_t["KD"]["PER_OBJECT"] = True
     return cfg, cfg_t
 
 

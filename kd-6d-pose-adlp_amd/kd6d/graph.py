@@ -99,6 +99,10 @@ class GraphedKDStep:
             snet.store.resolve_grads(self._split, snet.store.n_train)      # accumulated FPN + head gradients -> fp32
             D.exchange_slice(snet.store, self._split, snet.store.n_train)
 
+    def _per_object(self):
+        """The teacher selects its cells per (image, ground-truth slot) (PoseModuleKD.kd_per_object)."""
+        return bool(getattr(self.teacher, "kd_per_object", False))
+
     def _student_step(self, pred_t):
         if self._w is None:
             self._w = torch.tensor([self.w_cls, self.w_reg, self.w_kd], dtype=torch.float32,
@@ -194,7 +198,7 @@ class GraphedKDStep:
         for side, tgt in ((cur, self.tgt), (nxt, self.tgt_nxt)):
             tgt.rebind_block(side[1])
         cur[2].copy_(self.t_cur.flats[0]); cur[3].copy_(self.t_cur.flats[1])
-        self.t_cur = TeacherKnowledge.from_flats(cur[2], cur[3], self.t_cur.batch, self.t_cur.cap)
+        self.t_cur = TeacherKnowledge.from_flats(cur[2], cur[3], self.t_cur.batch, self.t_cur.cap, self.t_cur.per_object)
         self.teacher._teacher_flats = (nxt[2], nxt[3])     # the teacher's selection writes straight into the next block
         self._blocks = blocks
 
@@ -246,7 +250,8 @@ class GraphedKDStep:
             self._make_blocks()
         elif not self.pipeline and getattr(self.teacher, "_teacher_flats", None) is None:
             from .kd_losses import teacher_flats     # caller-owned teacher outputs: cleared by the teacher's prologue
-            self.teacher._teacher_flats = teacher_flats(self.images.tensors.shape[0], self.images.tensors.device)
+            self.teacher._teacher_flats = teacher_flats(self.images.tensors.shape[0], self.images.tensors.device,
+                                                        per_object=self._per_object())
         snap = self._snapshot()                              # the warm-up steps below must not train
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -425,7 +430,7 @@ class GroupedTeacherKDStep(GraphedKDStep):
 
     # ---- blocks ---------------------------------------------------------------------------------
     def _build_sides(self, x, tgt):
-        from .kd_losses import CAP, TeacherKnowledge
+        from .kd_losses import CAP, TeacherKnowledge, teacher_flat_sizes
         T = self.group
         B, _, H, W = x.shape
         if T * B * H * W >= 1 << 24:
@@ -440,8 +445,9 @@ class GroupedTeacherKDStep(GraphedKDStep):
         esz = torch.empty((), dtype=snet.dtype).element_size()
         img_b = B * H * W * 8 * esz
         tb = tgt.block_bytes()
-        n, nt = B * CAP, T * B * CAP
-        wf_b, wi_n = nt * 48 * 4, nt + (T * B + 3) // 4 * 4
+        per_object = self._per_object()
+        wf_n, wi_n = teacher_flat_sizes(T * B, CAP, per_object)      # one selection over the group's T * B images
+        wf_b = wf_n * 4
 
         def al(v):
             return (v + 255) // 256 * 256
@@ -462,12 +468,8 @@ class GroupedTeacherKDStep(GraphedKDStep):
                 sd.tgts.append(t)
             wf = sd.wf = blk[o_wf:o_wf + wf_b].view(torch.float32)
             wi = sd.wi = blk[o_wi:o_wi + wi_n * 4].view(torch.int32)
-            kp, kpn = wf[0:nt * 16].view(nt, 8, 2), wf[nt * 16:nt * 32].view(nt, 8, 2)
-            sc, beta = wf[nt * 32:nt * 40].view(nt, 8), wf[nt * 40:nt * 48].view(nt, 8)
             # the cells of slot s: a contiguous range of every slot array (they are image-major), no copies
-            sd.tk = [TeacherKnowledge(wi[nt + s * B:nt + (s + 1) * B], kp[s * n:(s + 1) * n], sc[s * n:(s + 1) * n],
-                                      wi[s * n:(s + 1) * n], kpn[s * n:(s + 1) * n], beta[s * n:(s + 1) * n], CAP, B)
-                     for s in range(T)]
+            sd.tk = TeacherKnowledge.group_views(wf, wi, T, B, CAP, per_object)
             sides.append(sd)
         self.sides = sides
         self._geom = (B, H, W)
@@ -477,6 +479,10 @@ class GroupedTeacherKDStep(GraphedKDStep):
         big = object.__new__(PackedTargets)                                       # what the teacher reads of the targets
         big.bbox_trans = torch.zeros((T * B,) + tuple(tgt.bbox_trans.shape[1:]), dtype=torch.float32, device=dev)
         big.frame_wh = tgt.frame_wh
+        if per_object:
+            # the per-object selection reads every image's classes and instance count
+            big.class_ids = torch.zeros((T * B,) + tuple(tgt.class_ids.shape[1:]), dtype=torch.int32, device=dev)
+            big.n_gt = torch.zeros(T * B, dtype=torch.int32, device=dev)
         if self._gate_reads_targets():
             # the teacher PnP gate also reads every image's intrinsics and 3D boxes
             big.K = torch.zeros((T * B,) + tuple(tgt.K.shape[1:]), dtype=torch.float32, device=dev)
@@ -543,6 +549,9 @@ class GroupedTeacherKDStep(GraphedKDStep):
         gate = self._gate_reads_targets()
         for s in range(T):
             self._tgt_big.bbox_trans[s * B:(s + 1) * B].copy_(P.tgts[s].bbox_trans, non_blocking=True)
+            if hasattr(self._tgt_big, "class_ids"):
+                self._tgt_big.class_ids[s * B:(s + 1) * B].copy_(P.tgts[s].class_ids, non_blocking=True)
+                self._tgt_big.n_gt[s * B:(s + 1) * B].copy_(P.tgts[s].n_gt, non_blocking=True)
             if gate:
                 self._tgt_big.K[s * B:(s + 1) * B].copy_(P.tgts[s].K, non_blocking=True)
                 self._tgt_big.kp3d[s * B:(s + 1) * B].copy_(P.tgts[s].kp3d, non_blocking=True)

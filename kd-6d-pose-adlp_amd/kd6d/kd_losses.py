@@ -17,6 +17,8 @@ ANCHOR_SIZES = [32, 64, 128, 256, 512]
 ANCHOR_STRIDES = [8, 16, 32, 64, 128]
 CAP = 32          # slots per image for teacher cells / pose candidates (one class: <= 12; the PnP kernels take <= 32)
 MAX_GT = _lib.MAX_GT
+PER_OBJECT_GATE_ERROR = ("--kd_per_object cannot be combined with --teacher_pnp_gate: the gate solves one pose per image "
+                         "from the image's cells, a per-object gate is not implemented")
 
 
 def positives_bound(positive_num, n_levels=_lib.MAX_SEG, instances=MAX_GT):
@@ -175,36 +177,68 @@ def _slot_starts(batch, cap, device):
     return t
 
 
-def teacher_flats(batch, device, cap=None):
-    """Caller-owned output buffers of teacher_select: fp32 (n*48) and int32 (n + batch rounded up to 4)."""
-    n = batch * (cap or CAP)
-    return (torch.zeros(n * 48, dtype=torch.float32, device=device),
-            torch.zeros(n + (batch + 3) // 4 * 4, dtype=torch.int32, device=device))
+def teacher_blocks(batch, per_object=False):
+    """Output blocks of a teacher selection: one per image, or one per (image, ground-truth slot) with per_object."""
+    return batch * (MAX_GT if per_object else 1)
+
+
+def teacher_flat_sizes(batch, cap=None, per_object=False):
+    """(fp32 elements, int32 elements) of the two buffers every slot array of a teacher selection is a view of: the
+    ONE place the layout's sizes come from (teacher_flats, TeacherKnowledge.from_flats, the hand-over blocks of
+    kd6d.graph)."""
+    blocks = teacher_blocks(batch, per_object)
+    n = blocks * (cap or CAP)
+    return n * 48, n + (blocks + 3) // 4 * 4
+
+
+def teacher_flats(batch, device, cap=None, per_object=False):
+    """Caller-owned output buffers of teacher_select: fp32 and int32, teacher_flat_sizes() elements."""
+    nf, ni = teacher_flat_sizes(batch, cap, per_object)
+    return (torch.zeros(nf, dtype=torch.float32, device=device), torch.zeros(ni, dtype=torch.int32, device=device))
 
 
 class TeacherKnowledge(dict):
     """pred_t of the reference (models/model_kd.py:83-92).  The device-side slot arrays are what the
-    student step consumes; the reference-named entries are materialised (with a sync) on demand."""
+    student step consumes; the reference-named entries are materialised (with a sync) on demand.
 
-    def __init__(self, t_cnt, t_kp, t_score, t_row, t_kp_norm, t_beta, cap, batch, flats=None):
+    per_object: the selection ran per (image, ground-truth slot) -- block o = b*MAX_GT + g holds the cells of class
+    class_ids[b, g] (kd6d_teacher_select_objects), `blocks` = batch*MAX_GT of them instead of `batch`."""
+
+    def __init__(self, t_cnt, t_kp, t_score, t_row, t_kp_norm, t_beta, cap, batch, flats=None, per_object=False):
         super().__init__()
         self.t_cnt, self.t_kp, self.t_score, self.t_row = t_cnt, t_kp, t_score, t_row
         self.t_kp_norm, self.t_beta = t_kp_norm, t_beta
         self.cap, self.batch = cap, batch
-        self.t_start = _slot_starts(batch, cap, t_cnt.device)
+        self.per_object = bool(per_object)
+        self.blocks = teacher_blocks(batch, per_object)
+        self.t_start = _slot_starts(self.blocks, cap, t_cnt.device)
         self.flats = flats            # (fp32, int32) buffers all the slot arrays are views of
 
     @staticmethod
-    def from_flats(wf, wi, batch, cap):
-        """Slot arrays as views of one fp32 (n*48) and one int32 (n + batch rounded up to 4) buffer."""
-        n, b = batch * cap, batch
+    def from_flats(wf, wi, batch, cap, per_object=False):
+        """Slot arrays as views of one fp32 and one int32 buffer of teacher_flat_sizes() elements."""
+        b = teacher_blocks(batch, per_object)
+        n = b * cap
+        assert (wf.numel(), wi.numel()) == teacher_flat_sizes(batch, cap, per_object), "teacher buffers of another layout"
         return TeacherKnowledge(wi[n:n + b], wf[0:n * 16].view(n, 8, 2), wf[n * 32:n * 40].view(n, 8), wi[0:n],
-                                wf[n * 16:n * 32].view(n, 8, 2), wf[n * 40:n * 48].view(n, 8), cap, b, (wf, wi))
+                                wf[n * 16:n * 32].view(n, 8, 2), wf[n * 40:n * 48].view(n, 8), cap, batch, (wf, wi),
+                                per_object)
+
+    @staticmethod
+    def group_views(wf, wi, group, batch, cap, per_object=False):
+        """`group` batches selected in ONE launch over group*batch images (buffers of teacher_flat_sizes(group*batch)):
+        the cells of batch s are a contiguous range of every slot array (they are image-major), no copies."""
+        big = TeacherKnowledge.from_flats(wf, wi, group * batch, cap, per_object)
+        b = teacher_blocks(batch, per_object)
+        n = b * cap
+        return [TeacherKnowledge(big.t_cnt[s * b:(s + 1) * b], big.t_kp[s * n:(s + 1) * n], big.t_score[s * n:(s + 1) * n],
+                                 big.t_row[s * n:(s + 1) * n], big.t_kp_norm[s * n:(s + 1) * n],
+                                 big.t_beta[s * n:(s + 1) * n], cap, batch, None, per_object) for s in range(group)]
 
     def clone_static(self):
         """Persistent copy (own storage) that `copy_from` refreshes: the double buffer of the step pipeline."""
         wf, wi = (t.clone() for t in self.flats)
-        return TeacherKnowledge.from_flats(wf, wi, self.batch, self.cap)
+        return TeacherKnowledge.from_flats(wf, wi, self.batch, self.cap, self.per_object)
 
     def copy_from(self, other):
         for mine, theirs in zip(self.flats, other.flats):
@@ -216,8 +250,8 @@ class TeacherKnowledge(dict):
         if key not in ("post_kp_2d", "post_kp_cls", "post_pos_per_img"):
             raise KeyError(key)
         cnt = self.t_cnt.cpu().tolist()
-        kp = torch.cat([self.t_kp[b * self.cap:b * self.cap + n] for b, n in enumerate(cnt)]) if self.batch else self.t_kp[:0]
-        sc = torch.cat([self.t_score[b * self.cap:b * self.cap + n] for b, n in enumerate(cnt)]) if self.batch else self.t_score[:0]
+        kp = torch.cat([self.t_kp[b * self.cap:b * self.cap + n] for b, n in enumerate(cnt)]) if self.blocks else self.t_kp[:0]
+        sc = torch.cat([self.t_score[b * self.cap:b * self.cap + n] for b, n in enumerate(cnt)]) if self.blocks else self.t_score[:0]
         self["post_kp_2d"], self["post_kp_cls"], self["post_pos_per_img"] = kp, sc, cnt
         return dict.__getitem__(self, key)
 
@@ -235,30 +269,42 @@ class DeferredTeacher:
 
 
 def teacher_select(cls_t, reg_t, levels, batch, bbox_trans, th=0.1, positive_num=10, positive_lambda=1.0, cap=CAP,
-                   frame_wh=(640.0, 480.0), flats=None, zeroed=False):
-    """flats: optional caller-owned (fp32 n*48, int32 n + batch rounded up to 4) output buffers (the step pipeline
-    keeps them inside its hand-over block); zeroed here unless the caller already did (zeroed=True: the teacher's
-    step prologue, ops.zero_many)."""
+                   frame_wh=(640.0, 480.0), flats=None, zeroed=False, per_object=False, class_ids=None, n_gt=None):
+    """flats: optional caller-owned output buffers (teacher_flat_sizes() elements; the step pipeline keeps them inside
+    its hand-over block); zeroed here unless the caller already did (zeroed=True: the teacher's step prologue,
+    ops.zero_many).  per_object: one selection per (image, ground-truth slot) on the class class_ids[b, g] for
+    g < n_gt[b] (both (batch, MAX_GT) / (batch,) int32 device tensors: PackedTargets.class_ids / .n_gt) instead of one
+    per image on the first class that emits."""
     dev = cls_t.device
     lv = make_levels(batch, levels)
-    n = batch * cap
+    nf, ni = teacher_flat_sizes(batch, cap, per_object)
     if flats is None:
-        wf = torch.zeros(n * 48, dtype=torch.float32, device=dev)        # one fill for all fp32 outputs
-        wi = torch.zeros(n + (batch + 3) // 4 * 4, dtype=torch.int32, device=dev)
+        wf = torch.zeros(nf, dtype=torch.float32, device=dev)        # one fill for all fp32 outputs
+        wi = torch.zeros(ni, dtype=torch.int32, device=dev)
     else:
         wf, wi = flats
-        assert wf.numel() == n * 48 and wi.numel() == n + (batch + 3) // 4 * 4
+        assert wf.numel() == nf and wi.numel() == ni
         if not zeroed:
             wf.zero_(); wi.zero_()
-    t_kp, t_kp_n = wf[0:n * 16].view(n, 8, 2), wf[n * 16:n * 32].view(n, 8, 2)
-    t_score, t_beta = wf[n * 32:n * 40].view(n, 8), wf[n * 40:n * 48].view(n, 8)
-    t_row, t_cnt = wi[0:n], wi[n:n + batch]
-    check(lib.kd6d_teacher_select(ctypes.byref(lv), ops._ptr(cls_t), ops._ptr(reg_t), ops._ptr(bbox_trans),
+    tk = TeacherKnowledge.from_flats(wf, wi, batch, cap, per_object)
+    P = ops._ptr
+    if per_object:
+        if class_ids is None or n_gt is None:
+            raise ValueError("teacher_select(per_object=True) needs the targets' class_ids and n_gt")
+        assert class_ids.dtype == torch.int32 and n_gt.dtype == torch.int32
+        assert class_ids.numel() == batch * MAX_GT and n_gt.numel() == batch
+        check(lib.kd6d_teacher_select_objects(ctypes.byref(lv), P(cls_t), P(reg_t), P(bbox_trans), P(class_ids), P(n_gt),
+                                              th, float(positive_num), float(positive_lambda), cap, frame_wh[0],
+                                              frame_wh[1], P(tk.t_cnt), P(tk.t_kp), P(tk.t_score), P(tk.t_row),
+                                              P(tk.t_kp_norm), P(tk.t_beta), ops._stream()),
+              "kd6d_teacher_select_objects")
+        return tk
+    check(lib.kd6d_teacher_select(ctypes.byref(lv), P(cls_t), P(reg_t), P(bbox_trans),
                                   th, float(positive_num), float(positive_lambda), cap, frame_wh[0], frame_wh[1],
-                                  ops._ptr(t_cnt), ops._ptr(t_kp), ops._ptr(t_score), ops._ptr(t_row),
-                                  ops._ptr(t_kp_n), ops._ptr(t_beta), ops._stream()),
+                                  P(tk.t_cnt), P(tk.t_kp), P(tk.t_score), P(tk.t_row),
+                                  P(tk.t_kp_norm), P(tk.t_beta), ops._stream()),
           "kd6d_teacher_select")
-    return TeacherKnowledge(t_cnt, t_kp, t_score, t_row, t_kp_n, t_beta, cap, batch, (wf, wi))
+    return tk
 
 
 class KDLoss:
@@ -284,6 +330,9 @@ class KDLoss:
         self.reach = -1.0 if reach is None else float(reach)
         self.weighted = bool(kd_cfg.get("WEIGHTED_OT", True))
         self.detach = bool(kd_cfg.get("DETACH", False))
+        # PER_OBJECT (--kd_per_object): one OT problem per (image, ground-truth slot) -- the student's positives of
+        # instance g against the teacher's cells of that instance's class -- instead of one per image
+        self.per_object = bool(kd_cfg.get("PER_OBJECT", False))
         if not self.weighted:
             raise NotImplementedError("unweighted OT (--weightedOT false) is not implemented on the HIP path")
         # every pick of a full image (MAX_GT instances) must fit: beyond `cap` the kernel truncates, and labels,
@@ -313,10 +362,36 @@ class KDLoss:
         key = (batch, str(device))
         ws = self._ws.get(key)
         if ws is None:
-            n, bp = batch * self.cap, (batch + 3) // 4 * 4
-            ws = self._ws[key] = (torch.zeros(8 + bp + n * 64 + 16, dtype=torch.float32, device=device),
-                                  torch.zeros(3 * bp + 4 + 2 * n, dtype=torch.int32, device=device))
+            nf, ni = self._ws_sizes(batch)
+            ws = self._ws[key] = (torch.zeros(nf, dtype=torch.float32, device=device),
+                                  torch.zeros(ni, dtype=torch.int32, device=device))
         return ws
+
+    def _ws_layout(self, batch):
+        """The ONE place the per-object part of the workspaces is laid out: ({name: (offset, elements)} fp32,
+        {name: ...} int32, fp32 total, int32 total).  "image" is the per-image layout forward() / assign() have always
+        used; per_object appends, behind it, the object-major copies xs_obj / g_xs_obj (n*16 each), alpha_obj /
+        g_alpha_obj (n*8 each), loss_obj (batch*MAX_GT) and obj_start / obj_cnt / valid_obj (batch*MAX_GT each), dest (n)."""
+        n, bp = batch * self.cap, (batch + 3) // 4 * 4
+        nobj = batch * MAX_GT
+        parts_f = [("image", 8 + bp + n * 64 + 16)]            # + the two loss sums' fixed-point workspaces
+        parts_i = [("image", 3 * bp + 4 + 2 * n)]
+        if self.per_object:
+            parts_f += [("xs_obj", n * 16), ("g_xs_obj", n * 16), ("alpha_obj", n * 8), ("g_alpha_obj", n * 8),
+                        ("loss_obj", nobj)]
+            parts_i += [("obj_start", nobj), ("obj_cnt", nobj), ("valid_obj", nobj), ("dest", n)]
+        out = []
+        for parts in (parts_f, parts_i):
+            seg, off = {}, 0
+            for name, cnt in parts:
+                seg[name] = (off, cnt)
+                off += cnt
+            out += [seg, off]
+        return out[0], out[2], out[1], out[3]
+
+    def _ws_sizes(self, batch):
+        """(fp32, int32) elements of the per-step workspaces."""
+        return self._ws_layout(batch)[2:]
 
     def assign(self, levels, batch, tgt, keys=None, prezeroed=False, step_counter=None):
         """SSC target assignment + the zeroed per-step workspaces.  Depends on the targets only, not on the student's
@@ -344,8 +419,9 @@ class KDLoss:
         if prezeroed:
             wf, wi = self.workspaces(batch, dev)
         else:
-            wf = torch.zeros(8 + bp + n * 64 + 16, **f32)     # + the two loss sums' fixed-point workspaces
-            wi = torch.zeros(3 * bp + 4 + 2 * n, **i32)
+            nf, ni = self._ws_sizes(batch)
+            wf = torch.zeros(nf, **f32)
+            wi = torch.zeros(ni, **i32)
         pos_cnt = wi[0:batch]
         pos_row, pos_gt = wi[3 * bp + 4:3 * bp + 4 + n], wi[3 * bp + 4 + n:3 * bp + 4 + 2 * n]
         P = ops._ptr
@@ -385,7 +461,39 @@ class KDLoss:
                                       P(tgt.class_ids), P(tgt.kp3d), P(tgt.rot), P(tgt.trans), P(tgt.bbox_trans),
                                       P(self.diameters), self.kinv, fw, fh, cap, P(xs), P(alpha), P(g_reg),
                                       P(losses[1:2]), P(ws_reg), P(s_start), st), "kd6d_student_points")
-        if teacher is not None:
+        if teacher is not None and bool(getattr(teacher, "per_object", False)) != self.per_object:
+            raise ValueError("KDLoss(PER_OBJECT=%s) got a teacher selection made with per_object=%s: both sides of the "
+                             "KD term must use the same mode" % (self.per_object, not self.per_object))
+        if teacher is not None and self.per_object:
+            # group the positives by instance -> one Sinkhorn problem per object (same kernel, batch*MAX_GT problems,
+            # teacher segments at o*cap) -> mean over the valid objects -> gradients back into slot order
+            nobj = batch * MAX_GT
+            if teacher.t_cnt.numel() != nobj:
+                raise ValueError("per-object KD: the teacher selection holds %d blocks, this batch has %d objects slots"
+                                 % (teacher.t_cnt.numel(), nobj))
+            seg_f, seg_i, nf, ni = self._ws_layout(batch)
+            assert wf.numel() == nf and wi.numel() == ni, "workspaces of another layout (made without PER_OBJECT?)"
+
+            def part(buf, seg, name):
+                off, cnt = seg[name]
+                return buf[off:off + cnt]
+
+            xs_o, g_xs_o = (part(wf, seg_f, k).view(n, 8, 2) for k in ("xs_obj", "g_xs_obj"))
+            al_o, g_al_o = (part(wf, seg_f, k).view(n, 8) for k in ("alpha_obj", "g_alpha_obj"))
+            loss_obj = part(wf, seg_f, "loss_obj")
+            o_start, o_cnt, o_valid, dest = (part(wi, seg_i, k) for k in ("obj_start", "obj_cnt", "valid_obj", "dest"))
+            check(lib.kd6d_kd_group_objects(P(pos_cnt), P(pos_gt), P(xs), P(alpha), batch, cap, P(o_start), P(o_cnt),
+                                            P(dest), P(xs_o), P(al_o), st), "kd6d_kd_group_objects")
+            check(lib.kd6d_sinkhorn_div_fwd_bwd(P(xs_o), P(al_o), P(o_start), P(o_cnt), P(teacher.t_kp_norm),
+                                                P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), nobj, self.p,
+                                                self.blur, self.scaling, self.reach, P(loss_obj), P(o_valid), None,
+                                                P(g_xs_o), P(g_al_o), st), "kd6d_sinkhorn_div_fwd_bwd")
+            check(lib.kd6d_kd_mean(P(loss_obj), P(o_valid), nobj, P(losses[2:3]), P(n_valid), st), "kd6d_kd_mean")
+            check(lib.kd6d_kd_scatter_objects(P(pos_cnt), P(pos_gt), P(dest), P(o_valid), P(g_xs_o), P(g_al_o), batch,
+                                              cap, P(g_xs), P(g_alpha), P(valid), st), "kd6d_kd_scatter_objects")
+            self.obj = dict(start=o_start, cnt=o_cnt, valid=o_valid, dest=dest, loss=loss_obj, xs=xs_o, alpha=al_o,
+                            g_xs=g_xs_o, g_alpha=g_al_o)
+        elif teacher is not None:
             check(lib.kd6d_sinkhorn_div_fwd_bwd(P(xs), P(alpha), P(s_start), P(pos_cnt), P(teacher.t_kp_norm),
                                                 P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), batch, self.p,
                                                 self.blur, self.scaling, self.reach, P(loss_img), P(valid), None,

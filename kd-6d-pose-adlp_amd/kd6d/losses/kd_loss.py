@@ -154,7 +154,9 @@ class KDPoseLoss:
     reference's dict or kd6d's TeacherKnowledge.  The positive subset of the SSC assignment is drawn from
     `self.keys` (uniform randoms, one per cell in packed order) when set, else from torch's generator.
     Deviations from the reference, as everywhere in this build: OT weights are gathered per
-    cell (mixed-class batches work), a batch without positives gives reg = kd = 0."""
+    cell (mixed-class batches work), a batch without positives gives reg = kd = 0.  cfg_kd["PER_OBJECT"] (additive):
+    the KD term is the mean over (image, ground-truth slot) of the divergence between that instance's positives and
+    the teacher's cells of its class; pred_t must then be a per-object TeacherKnowledge."""
 
     def __init__(self, gamma, alpha, anchor_sizes, anchor_strides, positive_type, positive_num, positive_lambda,
                  top_k, internal_K, diameters, target_coder, cfg_kd=None):
@@ -165,8 +167,10 @@ class KDPoseLoss:
             raise NotImplementedError("the HIP path implements LOSS_REG_TYPE=3D (got %r)" % (ttype,))
         self.anchor_sizes, self.anchor_strides = list(anchor_sizes), list(anchor_strides)
         self.cfg_kd = cfg_kd
+        # cfg_kd["PER_OBJECT"] (additive key of this build): one OT problem per (image, ground-truth slot)
+        self.per_object = bool(cfg_kd and cfg_kd.get("PER_OBJECT", False))
         self.impl = KDLoss(internal_K, diameters, gamma, alpha, positive_num, positive_lambda,
-                           cfg_kd if cfg_kd and "GTYPE" in cfg_kd else None)
+                           cfg_kd if cfg_kd and "GTYPE" in cfg_kd else ({"PER_OBJECT": True} if self.per_object else None))
         self.impl.anchor_sizes, self.impl.anchor_strides = self.anchor_sizes, self.anchor_strides
         if cfg_kd is not None:
             self.kd_loss = SamplesLoss(cfg_kd["GTYPE"], p=cfg_kd["GP"], blur=cfg_kd["GBLUR"],
@@ -193,6 +197,12 @@ class KDPoseLoss:
             x = torch.nn.functional.pad(x, (0, cpad - x.shape[1]))
         return x.contiguous()
 
+    def _check_pred_t(self, pred_t):
+        if self.per_object and pred_t is not None and not (isinstance(pred_t, TeacherKnowledge) and pred_t.per_object):
+            raise TypeError("KDPoseLoss(cfg_kd['PER_OBJECT']): pred_t must be the TeacherKnowledge of a per-object teacher "
+                            "forward (kd6d.kd_losses.teacher_select(per_object=True)); the reference's pred_t dict has no "
+                            "object axis")
+
     def __call__(self, pred_cls, pred_reg, targets, anchors, pred_t):
         dev = pred_cls[0].device
         if dev.type != "cuda":
@@ -201,6 +211,7 @@ class KDPoseLoss:
         levels = [tuple(t.shape[-2:]) for t in pred_cls]
         tgt = targets if isinstance(targets, PackedTargets) else PackedTargets(targets, dev)
         tgt.frame_wh = (float(self.w), float(self.h))
+        self._check_pred_t(pred_t)
         if pred_t is None or isinstance(pred_t, TeacherKnowledge):
             teacher = pred_t
         else:

@@ -81,9 +81,15 @@ class PoseModuleKD(nn.Module):
         # it on: with the host solver for eager launches only, with PNP_SOLVER = "device" (kd6d_teacher_pnp_gate on the
         # teacher's stream, no host round trip) in every launch mode
         self.teacher_pnp_gate = bool(cfg.get("RUNTIME", {}).get("TEACHER_PNP_GATE", False))
+        # cfg['KD']['PER_OBJECT'] (--kd_per_object): the KD term per (image, ground-truth slot).  The teacher module selects
+        # its cells per object, the student module's loss solves one OT problem per object; both read the same key
+        self.kd_per_object = bool(kd.get("PER_OBJECT", False))
+        if self.kd_per_object and self.teacher_pnp_gate:
+            raise ValueError(kd_losses.PER_OBJECT_GATE_ERROR)
         self.loss_evaluator = KDLoss(cfg["INPUT"]["INTERNAL_K"], cfg["DATASETS"]["MESH_DIAMETERS"],
                                      cfg["SOLVER"]["FOCAL_GAMMA"], cfg["SOLVER"]["FOCAL_ALPHA"], self.positive_num,
-                                     self.positive_lambda, kd if "GTYPE" in kd else None)
+                                     self.positive_lambda,
+                                     kd if "GTYPE" in kd else ({"PER_OBJECT": True} if self.kd_per_object else None))
         # ---- parameters / buffers under the reference names, as views of the flat store ----
         self._names = []
         for name, view, is_param in self.net.named_logical():
@@ -195,7 +201,8 @@ class PoseModuleKD(nn.Module):
         if is_teacher:
             # caller-owned output buffers (GraphedKDStep): cleared together with the statistics arena in one launch
             flats = getattr(self, "_teacher_flats", None)
-            if flats is not None and flats[0].numel() != B * kd_losses.CAP * 48:
+            if flats is not None and (flats[0].numel(), flats[1].numel()) != kd_losses.teacher_flat_sizes(
+                    B, kd_losses.CAP, self.kd_per_object):
                 flats = None                  # another batch size than the one the buffers were made for
             pre = flats is not None and net.scratch_region() is not None
             if pre:
@@ -204,7 +211,9 @@ class PoseModuleKD(nn.Module):
             tgt = targets if isinstance(targets, PackedTargets) else PackedTargets(targets, net.device)
             tk = kd_losses.teacher_select(cls, reg, net.levels, B, tgt.bbox_trans, self.inference_th,
                                           self.positive_num, self.positive_lambda, frame_wh=tgt.frame_wh,
-                                          flats=flats, zeroed=pre)
+                                          flats=flats, zeroed=pre, per_object=self.kd_per_object,
+                                          class_ids=tgt.class_ids if self.kd_per_object else None,
+                                          n_gt=tgt.n_gt if self.kd_per_object else None)
             if self.teacher_pnp_gate:
                 if self.pnp_solver == "device":
                     self._apply_pnp_gate_device(tk, cls, tgt)

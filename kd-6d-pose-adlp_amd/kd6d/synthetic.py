@@ -24,14 +24,75 @@ def cube_keypoints(diameters=MESH_DIAMETERS):
     return signs[None] * e[:, None, None]
 
 
-def make_batch(batch, seed, crop=256, mixed_classes=False, full_frame=False, class_id=0, class_offset=0):
+def _random_rotation(rng):
+    q, r = np.linalg.qr(rng.standard_normal((3, 3)))
+    q = q * np.sign(np.diag(r))[None, :]
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q.astype(np.float32)
+
+
+def batch_classes(image, instances=1, mixed_classes=False, class_id=0, class_offset=0):
+    """Classes of image `image` of a make_batch() batch, one per instance, all distinct.  One instance: class_id, or
+    with mixed_classes LINEMOD class (class_offset + image) mod 13.  Several: consecutive LINEMOD classes from there."""
+    if instances == 1:
+        return [LINEMOD_CLASSES[(class_offset + image) % len(LINEMOD_CLASSES)] if mixed_classes else class_id]
+    first = (class_offset + image) * instances if mixed_classes else (
+        LINEMOD_CLASSES.index(class_id) if class_id in LINEMOD_CLASSES else 0)
+    return [LINEMOD_CLASSES[(first + g) % len(LINEMOD_CLASSES)] for g in range(instances)]
+
+
+def teacher_cls_bias(instances=1, mixed_classes=False, class_id=0, hot=1.0, cold=-6.0):
+    """head.cls_logits.bias of a synthetic (random-weight) teacher: `hot` for every class a make_batch() batch with
+    these options can contain, `cold` elsewhere, so that the teacher emits cells for the objects in the batch."""
+    if mixed_classes:
+        present = set(LINEMOD_CLASSES)
+    else:
+        present = set(batch_classes(0, instances, False, class_id))
+    return [hot if c in present else cold for c in range(len(MESH_DIAMETERS))]
+
+
+def _make_multi(rng, imgs, batch, instances, crop, mixed_classes, full_frame, class_id, class_offset):
+    """make_batch() for 2..4 instances per image: objects of distinct classes, masks with ids 1..N as non-overlapping
+    rectangles, one per vertical strip (the last strip reaches the right edge, the last mask row stays free); the crop
+    is a scaled view centred on the principal point."""
+    K = np.asarray(INTERNAL_K, np.float32).reshape(3, 3)
+    kp3d = cube_keypoints()
+    H, W = (480, 640) if full_frame else (crop, crop)
+    N = instances
+    targets = []
+    for i in range(batch):
+        classes = batch_classes(i, N, mixed_classes, class_id, class_offset)
+        R = np.stack([_random_rotation(rng) for _ in range(N)])
+        T = np.stack([np.array([rng.normal(0, 60), rng.normal(0, 40), rng.uniform(700, 1600)], np.float32).reshape(3, 1)
+                      for _ in range(N)])
+        s = 1.0 if full_frame else float(rng.uniform(0.8, 1.6)) * crop / 256.0
+        tx, ty = (0.0, 0.0) if full_frame else (W / 2.0 - s * K[0, 2], H / 2.0 - s * K[1, 2])
+        bbox_trans = np.array([[s, 0, tx], [0, s, ty]], np.float32)
+        mask = np.zeros((H, W), np.float32)
+        for g in range(N):
+            x0, x1 = g * W // N + 1, ((g + 1) * W // N - 1 if g < N - 1 else W)
+            y0, y1 = int(rng.integers(0, max(H // 4, 1))), H - 1 - int(rng.integers(0, max(H // 4, 1)))
+            mask[y0:y1, x0:x1] = g + 1
+        targets.append(PoseAnnot(torch.from_numpy(kp3d.copy()), torch.from_numpy(K.copy()), torch.from_numpy(mask),
+                                 torch.tensor(classes, dtype=torch.long), torch.from_numpy(R),
+                                 torch.from_numpy(T), W, H, torch.tensor(float(s)), torch.from_numpy(bbox_trans)))
+    return ImageList(torch.from_numpy(imgs), [(H, W)] * batch), targets
+
+
+def make_batch(batch, seed, crop=256, mixed_classes=False, full_frame=False, class_id=0, class_offset=0, instances=1):
     """Returns (ImageList on CPU, list[PoseAnnot] on CPU).  mixed_classes: image i shows LINEMOD class
-    (class_offset + i) mod 13 (a rank passes its first global image index as class_offset)."""
+    (class_offset + i) mod 13 (a rank passes its first global image index as class_offset).  instances (1..4): objects
+    per image, of distinct classes (batch_classes) with disjoint masks; 1 = the single centred object below."""
+    if not 1 <= int(instances) <= 4:
+        raise ValueError("make_batch: instances must be in 1..4 (got %r)" % (instances,))
     rng = np.random.default_rng(seed)
     K = np.asarray(INTERNAL_K, np.float32).reshape(3, 3)
     kp3d = cube_keypoints()
     H, W = (480, 640) if full_frame else (crop, crop)
     imgs = rng.standard_normal((batch, 3, H, W), dtype=np.float32)
+    if int(instances) > 1:
+        return _make_multi(rng, imgs, batch, int(instances), crop, mixed_classes, full_frame, class_id, class_offset)
     targets = []
     for i in range(batch):
         c = LINEMOD_CLASSES[(class_offset + i) % len(LINEMOD_CLASSES)] if mixed_classes else class_id

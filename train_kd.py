@@ -35,7 +35,7 @@ from kd6d.libs.eval_libs import valid  # noqa: E402
 from kd6d.libs.train_libs import (build_dataset, build_model, build_model_teacher, dataset_meshes,  # noqa: E402
                                   start_exchange_after_graphs, stop_if_barrier_timeouts)
 from kd6d.models.model_kd import PoseModuleKD as PoseModule  # noqa: E402
-from kd6d.synthetic import make_batch  # noqa: E402
+from kd6d.synthetic import make_batch, teacher_cls_bias  # noqa: E402
 
 
 def synthetic_loader(cfg, device, n_batches=8):
@@ -45,7 +45,8 @@ def synthetic_loader(cfg, device, n_batches=8):
     for i in range(n_batches):
         images, targets = make_batch(per_gpu, 1000 * get_rank() + i, crop=size,
                                      mixed_classes=cfg["DATASETS"].get("MIXED_CLASSES", False),
-                                     class_offset=get_rank() * per_gpu)
+                                     class_offset=get_rank() * per_gpu,
+                                     instances=cfg["RUNTIME"].get("SYNTHETIC_INSTANCES", 1))
         batches.append((images.to(device), PackedTargets(targets, device), None))
     while True:
         for b in batches:
@@ -164,6 +165,14 @@ if __name__ == "__main__":
 
     print("Building teacher ......")
     model_t = build_model_teacher(cfg_t, PoseModule, device)
+    multi = cfg["RUNTIME"].get("SYNTHETIC_INSTANCES", 1) > 1 or cfg["KD"].get("PER_OBJECT", False)
+    if cfg["RUNTIME"]["SYNTHETIC"] and multi and not cfg_t["RUNTIME"].get("WEIGHT_FILE"):
+        # a random-weight teacher emits no cell above the confidence threshold: raise the class bias of every class the
+        # synthetic batches can contain, so that the KD term has teacher cells for every object
+        sd_t = model_t.state_dict()
+        bias = teacher_cls_bias(cfg["RUNTIME"].get("SYNTHETIC_INSTANCES", 1), cfg["DATASETS"].get("MIXED_CLASSES", False))
+        sd_t["head.cls_logits.bias"] = torch.tensor(bias[:sd_t["head.cls_logits.bias"].numel()])
+        model_t.load_state_dict(sd_t)
     print("Building student ......")
     model, optimizer, scheduler, total_steps = build_model(cfg, PoseModule, device)
     VAL_FREQ = cfg["SOLVER"]["VAL_FREQ"]
