@@ -89,9 +89,13 @@ int kd6d_abi_version(void);
  * {first element, element count, first workgroup, parts, slab address}, regions in ascending workgroup order,
  * total_blocks workgroups of 1024 elements each.  parts == 0: grads[e] += value(planar accumulator of element e, class
  * KD6D_ACC_GRAD), accumulator cleared.  parts >= 1: grads[first + i] += the sum over the `parts` partial images
- * slab[part][i] of `count` floats each (what kd6d_conv2d_wgrad wrote), in a fixed association: PG =
- * kd6d_grad_acc_resolve_part_groups(parts) interleaved partial sums (parts g, g + PG, ... in order), then those in g
- * order.  Workgroups per region: ceil(count / 1024) for parts == 0, ceil(count / (1024 / PG)) otherwise. */
+ * slab[part][i] of `count` floats each (what kd6d_conv2d_wgrad wrote), in a fixed association (fp32 throughout): PG =
+ * kd6d_grad_acc_resolve_part_groups(parts) groups; group g owns parts g, g + PG, g + 2 PG, ... and keeps FOUR running
+ * sums t_0 .. t_3 that start at 0, t_k adding parts g + k PG, g + (k + 4) PG, g + (k + 8) PG, ... in that order; the
+ * group's sum is (t_0 + t_1) + (t_2 + t_3); the PG group sums are added in g order and that total is added to grads.
+ * (Up to three parts per group this equals adding them one after the other; beyond, it does not.)  PG is 1 for parts
+ * <= 16 and doubles at 32, 64, 128 and 256 parts, 32 at most.  tests/optim_ref.py: slab_sum is this sentence in numpy.
+ * Workgroups per region: ceil(count / 1024) for parts == 0, ceil(count / (1024 / PG)) otherwise. */
 typedef struct kd6d_acc { int64_t lo, hi; } kd6d_acc;
 /* Workspace of a launch that reduces to ONE fp32 scalar (kd6d_focal_fwd, kd6d_student_points' loss_reg):
  * 32 bytes, pre-zeroed; the launch's LAST workgroup converts the fixed-point total and WRITES the scalar (the running
@@ -209,8 +213,8 @@ int kd6d_conv2d_dgrad(const kd6d_conv_geom* g, int dtype, const void* dy,
  * workgroups and split s stores its partial dW, all cout*k*k*cin floats, at dw_slab + s * cout*k*k*cin (plain stores;
  * every element of every part is written).  kd6d_conv2d_wgrad_parts() tells how many parts the launch writes for a
  * geometry, dtype, bias flag and cu_budget (>= 1; a deterministic function of its arguments and the device);
- * slab_floats is checked against it.  The caller adds the parts in order (kd6d_grad_acc_resolve; "reproducible
- * reductions").  dbias_acc (optional): += sum_pixels dy, the bias gradient of the same layer, taken from the dY tiles the
+ * slab_floats is checked against it.  The caller adds the parts in a fixed association (kd6d_grad_acc_resolve;
+ * "reproducible reductions").  dbias_acc (optional): += sum_pixels dy, the bias gradient of the same layer, taken from the dY tiles the
  * kernel stages anyway, into PLANAR accumulators (class KD6D_ACC_GRAD, stride acc_hi_stride).
  * cu_budget: how many compute units this launch should aim to fill (0 = the whole device): a caller that keeps k
  * weight gradients in flight on k streams passes CUs/k -- same k-loop work, 1/k of the partial images. */

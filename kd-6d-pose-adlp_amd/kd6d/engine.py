@@ -166,7 +166,8 @@ class ParamStore:
 
     def resolve_grads(self, lo=0, hi=None):
         """grads[lo:hi] += the gradients that were summed across workgroups, for every marked entry in that range:
-        fixed-point accumulators (cleared) and partial-image slabs (added in part order).  One launch
+        fixed-point accumulators (cleared) and partial-image slabs (left as they are; added in the fixed association
+        include/kd6d.h states).  One launch
         (kd6d_grad_acc_resolve); the region table is built on first use -- outside any stream capture."""
         hi = self.n_train if hi is None else hi
         plan = self._resolve_plans.get((lo, hi))

@@ -271,7 +271,9 @@ def conv2d_wgrad(geom, x, dy, dw_slab, flops=0, dbias=None, acc_stride=0, cu_bud
 
 def conv2d_wgrad_f32(geom, x, dy, with_bias=False, cu_budget=0):
     """Stand-alone weight gradient -> fp32 tensors (dw, dbias | None): slab and bias accumulators made, filled and
-    reduced here (torch arithmetic on the device: tests and tools; the engine resolves with kd6d_grad_acc_resolve)."""
+    reduced here (torch arithmetic on the device: tests and tools; the engine resolves with kd6d_grad_acc_resolve).
+    The parts are added one after the other, which is NOT the association of kd6d_grad_acc_resolve (include/kd6d.h:
+    groups of four running sums): the same value up to the rounding of an fp32 sum, other bits from four parts on."""
     nw = geom.cout * geom.ksize * geom.ksize * geom.cin
     parts = conv2d_wgrad_parts(geom, x.dtype, with_bias, cu_budget)
     slab = torch.empty(parts, nw, dtype=torch.float32, device=x.device)
@@ -279,7 +281,7 @@ def conv2d_wgrad_f32(geom, x, dy, with_bias=False, cu_budget=0):
     conv2d_wgrad(geom, x, dy, slab, dbias=acc[:geom.cout] if with_bias else None, acc_stride=geom.cout,
                  cu_budget=cu_budget)
     dw = slab[0].clone()
-    for k in range(1, parts):              # the order kd6d_grad_acc_resolve adds them in
+    for k in range(1, parts):              # in part order (see the docstring)
         dw += slab[k]
     return dw, (planar_acc_value(acc) if with_bias else None)
 
