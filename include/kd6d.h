@@ -454,7 +454,18 @@ int kd6d_image_to_nhwc(int dtype, const float* img_nchw, void* out, int B, int C
  * weights alpha[(..)*8+k] and teacher points/weights likewise; reach <= 0 means balanced.
  * Outputs: loss_img[b] = sum_k S_k (0 when a set is empty: valid_img[b] = 0; -1 = set larger than
  * kd6d_sinkhorn_max_points()), loss_kp (optional, n_images*8) = the eight S_k themselves (what SamplesLoss returns
- * for a batch of 8 problems), grad_xs / grad_alpha = d loss_img / d xs, alpha. */
+ * for a batch of 8 problems), grad_xs / grad_alpha = d loss_img / d xs, alpha.
+ * What is written: grad_xs / grad_alpha rows of problems with valid_img[b] <= 0, and rows that lie in no segment,
+ *   are NOT written (callers that scatter or sum whole arrays zero them first, as ops.sinkhorn_div does); loss_img[b]
+ *   and the eight loss_kp of such problems are 0.  loss_img[b] is the fp32 sum of the eight loss_kp in keypoint order.
+ *   Segments may lie in any order, with gaps; a problem's results depend on its own rows only (two launches, or
+ *   the problem launched alone, agree bitwise), and permuting the keypoint axis of all inputs permutes the results.
+ * Small sets: when both sets hold <= 16 points the four softmins of an update run side by side on the four 16-lane
+ *   rows of a wave (option sinkhorn.lanes = 0: the general path for every size).  Both paths give bitwise the same
+ *   grad_xs / grad_alpha; loss_img / loss_kp differ in the last bits (another summation order).
+ * Schedule: geomloss' epsilon_schedule evaluated in double from the fp32 box diagonal of the problem's 8*(N+M)
+ *   points (clamped to 1e-12); the geometric part is capped at 4096 steps, which differs from geomloss when scaling
+ *   is so close to 1 that ln(diameter/blur)/ln(1/scaling) exceeds that. */
 int kd6d_sinkhorn_div_fwd_bwd(const float* xs, const float* alpha, const int32_t* s_start,
                               const int32_t* s_cnt, const float* yt, const float* beta,
                               const int32_t* t_start, const int32_t* t_cnt, int n_images, float p, float blur,
