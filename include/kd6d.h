@@ -629,6 +629,31 @@ int kd6d_dzi_crop(const uint8_t* frames_bgr, const float* masks, int B, int H, i
                   const float* lut_rgb, int out_res, float* images_nchw, float* masks_out, float* bbox_trans,
                   float* bbox_scale, void* stream);
 
+/* ---- device-resident frame cache (csrc/frame_cache.hip; added under ABI 11, new symbols only): the decoded frames of
+ * a whole image list stay in device memory and a batch is assembled from sampler indices (kd6d/libs/frame_cache.py,
+ * train_kd.py / test.py --frame_cache device).  Pure data movement: the outputs are byte for byte what the host loader
+ * uploads, and kd6d_dzi_crop / the augmentation front-end consume them unchanged.
+ * kd6d_cache_gather_frames: frames_u8 (n,H,W,3) BGR and masks_u8 (n,H,W) merged instance ids; index_dev (B) int32;
+ *   frames_out_u8 (B,H,W,3) = frames_u8[index[b]], masks_out_f32 (B,H,W) = float(masks_u8[index[b]]).  No alignment is
+ *   required of any pointer beyond masks_out_f32's own 4 bytes, nor of H*W*3: lanes move 16-byte granules where source
+ *   and destination of a frame can both be aligned to them, 4-byte or single bytes otherwise, heads and tails bytewise.
+ *   An index outside [0, n) is never dereferenced: that batch entry is zero-filled (the host validates before upload).
+ * kd6d_cache_gather_targets: the small fields of a batch in the packed layout of kd6d.kd_losses.PackedTargets, one
+ *   launch.  table_f (n, KD6D_CACHE_ROW_F) = per frame {K 9, rot KD6D_MAX_GT*9, trans KD6D_MAX_GT*3}, table_i
+ *   (n, KD6D_CACHE_ROW_I) = {n_gt, class_ids KD6D_MAX_GT}, both zero-padded behind n_gt instances; kp3d (kp_elems =
+ *   classes*24, a multiple of 4): the 3D box corners, the same for every frame; bbox_trans (B,2,3): the output of the
+ *   kd6d_dzi_crop launch of this batch (copied, not recomputed: the packed block is the host path's bit for bit).
+ *   flat_f_out = {kp3d B*kp_elems | K B*9 | bbox_trans B*6 | rot B*MAX_GT*9 | trans B*MAX_GT*3}, flat_i_out =
+ *   {class_ids B*MAX_GT | n_gt B}, every field rounded up to 4 elements, the padding written as zero.  An index
+ *   outside [0, n) yields an image without instances. */
+#define KD6D_CACHE_ROW_F (9 + KD6D_MAX_GT * 12)
+#define KD6D_CACHE_ROW_I (1 + KD6D_MAX_GT)
+int kd6d_cache_gather_frames(const uint8_t* frames_u8, const uint8_t* masks_u8, int n, int H, int W,
+                             const int32_t* index_dev, int B, uint8_t* frames_out_u8, float* masks_out_f32, void* stream);
+int kd6d_cache_gather_targets(const float* table_f, const int32_t* table_i, const float* kp3d, int kp_elems, int n,
+                              const int32_t* index_dev, int B, const float* bbox_trans, float* flat_f_out,
+                              int32_t* flat_i_out, void* stream);
+
 /* ---- train-time augmentation of full frames (csrc/augment.hip): the reference's train transform chain
  * (libs/train_libs.py:212-238: Resize, RandomOcclusion, RandomShiftScaleRotate, RandomHSV, RandomSmooth,
  * RandomNoise, Grayscalize) and remove_invalids (poses.py:172-200), on the uint8 BGR frames (B,H,W,3) and float

@@ -60,6 +60,7 @@ class BnIn(ctypes.Structure):
 
 
 MAX_GT = 4
+CACHE_ROW_F, CACHE_ROW_I = 9 + MAX_GT * 12, 1 + MAX_GT      # KD6D_CACHE_ROW_F / _I: annotation table rows of the frame cache
 AUG_MAX_ID = 16                      # KD6D_AUG_MAX_ID: mask ids kd6d_aug_mask_stats / _relabel take
 MAX_ZERO = 8
 POSE_ERR_MAX_V = 1000                # KD6D_POSE_ERR_MAX_V: vertices kd6d_pose_errors scores per problem
@@ -163,6 +164,8 @@ SIGNATURES = {
     "kd6d_kd_group_objects": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "kd6d_kd_scatter_objects": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kd6d_dzi_crop": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P],
+    "kd6d_cache_gather_frames": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "kd6d_cache_gather_targets": [_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P],
     "kd6d_aug_warp_u8": [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P],
     "kd6d_aug_mask_stats": [_P, _I, _I, _I, _I, _P, _P],
     "kd6d_aug_occlude": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _D, ctypes.c_uint64, _P],

@@ -3,7 +3,7 @@
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
---synthetic_instances; yaml files may name a `_BASE_` file.
+--synthetic_instances, --frame_cache, --frame_cache_gb; yaml files may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -97,7 +97,33 @@ def get_argparser():
                         "correct for one object per image only).  Not with --teacher_pnp_gate")
     p.add_argument("--synthetic_instances", type=int, default=1, choices=[1, 2, 3, 4],
                    help="--synthetic: objects of distinct classes per image (masks in vertical strips)")
+    add_frame_cache_flags(p)
     return p
+
+
+FRAME_CACHE_SYNTHETIC_ERROR = ("--frame_cache device cannot be combined with --synthetic: synthetic batches are made on the "
+                               "device already and there is no image list to cache")
+
+
+def add_frame_cache_flags(p):
+    """The two flags train_kd.py and test.py share (kd6d/libs/frame_cache.py)."""
+    p.add_argument("--frame_cache", type=str, default="off", choices=["off", "device"],
+                   help="real data: device = decode every frame of the train / valid / test lists once, keep frames, "
+                        "instance masks and annotations in device memory and assemble the batches there "
+                        "(csrc/frame_cache.hip); same sampler, jitter, augmentation and crop, so the batches are the host "
+                        "loader's.  Data-parallel runs: EVERY rank caches the whole list (the distributed sampler draws "
+                        "from all of it each epoch), so the memory is needed per GPU.  Not with --synthetic")
+    p.add_argument("--frame_cache_gb", type=float, default=64.,
+                   help="--frame_cache device: most GiB of frames + masks one cached list may take per process; a list "
+                        "that does not fit is refused before anything is allocated (no fall-back to the host loader)")
+
+
+def frame_cache_runtime(args):
+    """-> the RUNTIME keys of the two flags; refuses --frame_cache device --synthetic."""
+    mode = getattr(args, "frame_cache", "off")
+    if mode != "off" and bool(getattr(args, "synthetic", False)):
+        raise SystemExit(FRAME_CACHE_SYNTHETIC_ERROR)
+    return dict(FRAME_CACHE=mode, FRAME_CACHE_GB=float(getattr(args, "frame_cache_gb", 64.)))
 
 
 def load_yaml(path):
@@ -138,6 +164,7 @@ def build_cfgs(args):
     cfg["RUNTIME"]["WORKING_DIR"] = args.working_dir
     cfg["RUNTIME"]["SYNTHETIC"] = bool(args.synthetic)
     cfg["RUNTIME"]["AUGMENT"] = bool(getattr(args, "augment", False))
+    cfg["RUNTIME"].update(frame_cache_runtime(args))
     cfg["RUNTIME"]["SKIP_TEACHER_EVAL"] = bool(args.skip_teacher_eval)
     cfg["RUNTIME"]["LAUNCH"] = args.launch
     cfg["RUNTIME"]["TEACHER_GROUP"] = max(1, int(args.teacher_group))

@@ -79,6 +79,36 @@ class PackedTargets:
     _SMALL_F = ("kp3d", "K", "bbox_trans", "rot", "trans")
     _SMALL_I = ("class_ids", "n_gt")
 
+    @classmethod
+    def from_packed(cls, mask, flat_f, flat_i, batch):
+        """A batch whose small fields are already packed on the device (kd6d_cache_gather_targets wrote flat_f / flat_i
+        in the layout of _SMALL_F / _SMALL_I): adopts the three buffers, then moves them into one block exactly as
+        __init__ does.  mask (batch, h, w) float32; the class count follows from flat_f's size."""
+        B = int(batch)
+        assert mask.dtype == torch.float32 and mask.dim() == 3 and mask.shape[0] == B and mask.is_contiguous()
+        assert flat_f.dtype == torch.float32 and flat_i.dtype == torch.int32
+        up = lambda v: (v + 3) // 4 * 4
+        kp = flat_f.numel() - (up(B * 9) + up(B * 6) + up(B * MAX_GT * 9) + up(B * MAX_GT * 3))
+        if kp <= 0 or kp % (B * 24) or flat_i.numel() != up(B * MAX_GT) + up(B):
+            raise ValueError("PackedTargets.from_packed: buffers of %d fp32 / %d int32 elements are not the packed layout "
+                             "of %d images" % (flat_f.numel(), flat_i.numel(), B))
+        out = object.__new__(cls)
+        out.batch = B
+        out.mask, out.flat_f, out.flat_i = mask, flat_f, flat_i
+        out.mask_h, out.mask_w = int(mask.shape[1]), int(mask.shape[2])
+        shapes = dict(kp3d=(B, kp // (B * 24), 8, 3), K=(B, 3, 3), bbox_trans=(B, 2, 3), rot=(B, MAX_GT, 3, 3),
+                      trans=(B, MAX_GT, 3), class_ids=(B, MAX_GT), n_gt=(B,))
+        for names, flat in ((cls._SMALL_F, flat_f), (cls._SMALL_I, flat_i)):
+            off = 0
+            for n in names:
+                cnt = int(np.prod(shapes[n]))
+                setattr(out, n, flat[off:off + cnt].view(shapes[n]))
+                off += up(cnt)
+        out.frame_wh = (640.0, 480.0)
+        out.block = None
+        out._into_block(torch.zeros(out.block_bytes(), dtype=torch.uint8, device=mask.device))
+        return out
+
     def _pack_small(self):
         """Re-home the small per-image fields as views of one fp32 and one int32 buffer (8 tensors -> 2)."""
         for names, attr in ((self._SMALL_F, "flat_f"), (self._SMALL_I, "flat_i")):

@@ -170,6 +170,17 @@ class DziLoader:
             yield ImageList(images, [(R, R)] * B), PackedTargets(out, dev), metas
 
     def _iter_augment(self):
+        dev = self.device
+        for batch in self.loader:
+            if len(batch) != 5:
+                raise ValueError("DziLoader(augment=True) needs a dataset built with augment (BOP_Dataset(augment=cfg))")
+            frames, masks, targets, metas, params = batch
+            yield self._augment_batch(frames.to(dev, non_blocking=True).contiguous(),
+                                      masks.to(dev, non_blocking=True).contiguous(), targets, metas, params)
+
+    def _augment_batch(self, frames, masks, targets, metas, params):
+        """Device frames / float masks of one batch, the items' PoseAnnots and collated parameters -> the yielded triple:
+        the augmentation front-end, the DZI crop around the remapped pose's box, the targets from the remapped poses."""
         from ..kd_losses import PackedTargets
         from .dataset import projected_box
         from .dzi_libs import aug_bbox_DZI, dzi_batch, test_bbox_DZI
@@ -177,33 +188,119 @@ class DziLoader:
         dev = self.device
         K = torch.tensor(self.front.ac.K, dtype=torch.float32)
         H, W = self.size
-        for batch in self.loader:
-            if len(batch) != 5:
-                raise ValueError("DziLoader(augment=True) needs a dataset built with augment (BOP_Dataset(augment=cfg))")
-            frames, masks, targets, metas, params = batch
-            frames, masks, poses = self.front.run(frames.to(dev, non_blocking=True).contiguous(),
-                                                  masks.to(dev, non_blocking=True).contiguous(), targets, params)
-            B = frames.shape[0]
-            annots, centers, scales = [], [], []
-            for t, (cls, Rs, Ts) in zip(targets, poses):
-                a = PoseAnnot(t.keypoints_3d, K, None, torch.from_numpy(cls), torch.from_numpy(Rs).reshape(-1, 3, 3),
-                              torch.from_numpy(Ts).reshape(-1, 3, 1), W, H)
-                box = projected_box(a, 0) if len(cls) else np.array([0.0, 0.0, float(W), float(H)])
-                c, s = aug_bbox_DZI(box, H, W) if self.training else test_bbox_DZI(box, H, W)
-                centers.append(c); scales.append(s)
-                annots.append(a)
+        frames, masks, poses = self.front.run(frames, masks, targets, params)
+        B = frames.shape[0]
+        annots, centers, scales = [], [], []
+        for t, (cls, Rs, Ts) in zip(targets, poses):
+            a = PoseAnnot(t.keypoints_3d, K, None, torch.from_numpy(cls), torch.from_numpy(Rs).reshape(-1, 3, 3),
+                          torch.from_numpy(Ts).reshape(-1, 3, 1), W, H)
+            box = projected_box(a, 0) if len(cls) else np.array([0.0, 0.0, float(W), float(H)])
+            c, s = aug_bbox_DZI(box, H, W) if self.training else test_bbox_DZI(box, H, W)
+            centers.append(c); scales.append(s)
+            annots.append(a)
+        images, crop_masks, trans, bscale = dzi_batch(frames, masks, np.stack(centers), np.asarray(scales), self.lut)
+        R = images.shape[-1]
+        out = [PoseAnnot(a.keypoints_3d.to(dev), a.K.to(dev), crop_masks[i], a.class_ids.to(dev), a.rotations.to(dev),
+                         a.translations.to(dev), R, R, bscale[i], trans[i]) for i, a in enumerate(annots)]
+        return ImageList(images, [(R, R)] * B), PackedTargets(out, dev), metas
+
+
+class _Indices(torch.utils.data.Dataset):
+    """Item i is i: a DataLoader over it yields the sampler's index batches and moves the RNGs exactly as the host
+    loader's DataLoader does (the base seed an iterator draws, then the sampler's own)."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return int(i)
+
+
+class CachedDziLoader(DziLoader):
+    """DziLoader over a device-resident frame cache (--frame_cache device; kd6d/libs/frame_cache.py): same length, same
+    `.loader.dataset`, same yielded triple, and -- with NUM_WORKERS=0 on the host side -- the same bytes, because the same
+    sampler object orders the frames, the same `random` / numpy draws follow in the same order and the gathered frames
+    go through the unchanged kd6d_dzi_crop / AugmentFront.  `loader` is the host DataLoader the run would have used; it
+    is kept for its length, data set and sampler and never iterated."""
+
+    def __init__(self, loader, cfg, device, training, augment=False, budget_bytes=64 * 2 ** 30, log=print):
+        from .frame_cache import DeviceFrameCache
+        super().__init__(loader, cfg, device, training, augment=augment)
+        self.cache = DeviceFrameCache(loader.dataset, device, budget_bytes,
+                                      num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0), log=log)
+        H, W = self.cache.H, self.cache.W
+        if self.front is None and (H, W) != tuple(self.size):
+            raise ValueError("frames are %dx%d but INPUT.INTERNAL_* is %dx%d: the CPU Resize transform of the reference "
+                             "is not rebuilt, store the frames at the internal resolution" % (W, H, self.size[1], self.size[0]))
+        self.indices = torch.utils.data.DataLoader(_Indices(len(loader.dataset)), batch_size=loader.batch_size,
+                                                   sampler=loader.sampler, num_workers=0, collate_fn=list,
+                                                   drop_last=loader.drop_last)
+
+    def __iter__(self):
+        from .. import ops
+        from ..kd_losses import PackedTargets
+        from .dzi_libs import aug_bbox_DZI, dzi_batch, test_bbox_DZI
+        from .poses import ImageList
+        if self.front is not None:
+            yield from self._iter_augment()
+            return
+        c = self.cache
+        H, W = c.H, c.W
+        for idx in self.indices:
+            slots = [c.resolve(i) for i in idx]
+            B = len(slots)
+            centers, scales = [], []
+            for s in slots:
+                ctr, sc = aug_bbox_DZI(c.boxes[s], H, W) if self.training else test_bbox_DZI(c.boxes[s], H, W)
+                centers.append(ctr); scales.append(sc)
+            index, frames, masks = c.gather(slots)
             images, crop_masks, trans, bscale = dzi_batch(frames, masks, np.stack(centers), np.asarray(scales), self.lut)
+            flat_f, flat_i = ops.cache_gather_targets(c.table_f_dev, c.table_i_dev, c.kp3d_dev, index, trans)
             R = images.shape[-1]
-            out = [PoseAnnot(a.keypoints_3d.to(dev), a.K.to(dev), crop_masks[i], a.class_ids.to(dev), a.rotations.to(dev),
-                             a.translations.to(dev), R, R, bscale[i], trans[i]) for i, a in enumerate(annots)]
-            yield ImageList(images, [(R, R)] * B), PackedTargets(out, dev), metas
+            yield (ImageList(images, [(R, R)] * B), PackedTargets.from_packed(crop_masks, flat_f, flat_i, B),
+                   [c.metas[s] for s in slots])
+
+    def _iter_augment(self):
+        from .augment import collate_params, draw_params
+        c = self.cache
+        ac = self.front.ac
+        bbox_3d = c.kp3d_host.numpy()
+        for idx in self.indices:
+            # per index, in batch order: the resample draws, then the item's augmentation parameters -- the order in which
+            # BOP_Dataset.__getitem__ consumes `random` without workers
+            slots, params = [], []
+            for i in idx:
+                s = c.resolve(i)
+                m = c.metas[s]
+                slots.append(s)
+                params.append(draw_params(ac, m["K"], m["class_ids"], m["rotations"], m["translations"], bbox_3d))
+            _, frames, masks = c.gather(slots)
+            yield self._augment_batch(frames, masks, [c.targets[s] for s in slots], [c.metas[s] for s in slots],
+                                      collate_params(params))
 
 
-def build_dataset(cfg, device="cuda", augment=False):
+FRAME_CACHE_MODES = ("off", "device")
+
+
+def _wrap_loader(loader, cfg, device, training, augment, frame_cache, frame_cache_gb):
+    if frame_cache not in FRAME_CACHE_MODES:
+        raise ValueError("frame_cache must be one of %s (got %r)" % (FRAME_CACHE_MODES, frame_cache))
+    if frame_cache == "device":
+        return CachedDziLoader(loader, cfg, device, training, augment=augment,
+                               budget_bytes=int(float(frame_cache_gb) * 2 ** 30))
+    return DziLoader(loader, cfg, device, training, augment=augment)
+
+
+def build_dataset(cfg, device="cuda", augment=False, frame_cache="off", frame_cache_gb=64.):
     """libs/train_libs.py:209-291: (train_loader, valid_loader) over the BOP image lists of cfg['DATASETS'], batch
     = IMS_PER_BATCH / N_GPU per rank, DistributedSampler semantics of libs/distributed.py.  DATASETS.TRAIN may be one
     list file or several (configs/linemod13.yaml): the datasets are concatenated.  augment=True runs the reference's
-    train transform chain on the training batches (DziLoader); the valid loader is untouched."""
+    train transform chain on the training batches (DziLoader); the valid loader is untouched.  frame_cache="device"
+    (train_kd.py --frame_cache device): both loaders are CachedDziLoaders -- every frame decoded once and kept in device
+    memory, at most frame_cache_gb GiB per loader and process; same samplers, same batches."""
     from torch.utils.data import ConcatDataset, DataLoader
     from .dataset import BOP_Dataset, collate_frames
     ds = cfg["DATASETS"]
@@ -233,13 +330,13 @@ def build_dataset(cfg, device="cuda", augment=False):
         return DataLoader(dset, batch_size=per_gpu, sampler=smp, num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0),
                           collate_fn=collate_frames, drop_last=shuffle)
 
-    return (DziLoader(loader(train_set, True), cfg, device, True, augment=bool(augment)),
-            DziLoader(loader(valid_set, False), cfg, device, False))
+    return (_wrap_loader(loader(train_set, True), cfg, device, True, bool(augment), frame_cache, frame_cache_gb),
+            _wrap_loader(loader(valid_set, False), cfg, device, False, False, frame_cache, frame_cache_gb))
 
 
-def build_test_dataset(cfg, device="cuda"):
+def build_test_dataset(cfg, device="cuda", frame_cache="off", frame_cache_gb=64.):
     """test.py:74-134 of the reference: the valid-style loader (no shuffle, no augmentation, DZI crop) over the image
-    list(s) of DATASETS.TEST, for one process."""
+    list(s) of DATASETS.TEST, for one process.  frame_cache / frame_cache_gb: as in build_dataset."""
     from torch.utils.data import ConcatDataset, DataLoader
     from .dataset import BOP_Dataset, collate_frames
     ds = cfg["DATASETS"]
@@ -249,7 +346,7 @@ def build_test_dataset(cfg, device="cuda"):
     per_gpu = int(cfg.get("TEST", {}).get("IMS_PER_BATCH", cfg["SOLVER"]["IMS_PER_BATCH"]))
     loader = DataLoader(dset, batch_size=per_gpu, sampler=torch.utils.data.SequentialSampler(dset),
                         num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0), collate_fn=collate_frames)
-    return DziLoader(loader, cfg, device, False)
+    return _wrap_loader(loader, cfg, device, False, False, frame_cache, frame_cache_gb)
 
 
 def dataset_meshes(loader):

@@ -785,3 +785,51 @@ class WgradGroup:
             check(lib.kd6d_wgrad_group_launch(_ptr(ent["plan"]), ent["info"][0], ent["info"][1], _ptr(ent["slab"]),
                                               _stream()), "kd6d_wgrad_group_launch")
         self.items, self.flops = [], 0
+
+
+# ---- device-resident frame cache (csrc/frame_cache.hip; kd6d/libs/frame_cache.py) ---------------------------------
+def cache_target_sizes(batch, kp_elems):
+    """(fp32, int32) elements of the packed small fields of a PackedTargets of `batch` images: kd6d_cache_gather_targets'
+    outputs, the layout of PackedTargets._SMALL_F / _SMALL_I (every field rounded up to 4 elements)."""
+    up = lambda v: (v + 3) // 4 * 4
+    g = _lib.MAX_GT
+    return (up(batch * kp_elems) + up(batch * 9) + up(batch * 6) + up(batch * g * 9) + up(batch * g * 3),
+            up(batch * g) + up(batch))
+
+
+def cache_gather_frames(frames, masks, index, frames_out=None, masks_out=None):
+    """frames (n,H,W,3) uint8, masks (n,H,W) uint8, index (B) int32, all on the device -> (frames[index] uint8,
+    masks[index] as float32).  frames_out / masks_out: optional caller-owned outputs (contiguous views are fine)."""
+    assert frames.dtype == torch.uint8 and masks.dtype == torch.uint8 and index.dtype == torch.int32
+    n, H, W, C = frames.shape
+    assert C == 3 and tuple(masks.shape) == (n, H, W)
+    B = int(index.numel())
+    if frames_out is None:
+        frames_out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=frames.device)
+    if masks_out is None:
+        masks_out = torch.empty((B, H, W), dtype=torch.float32, device=frames.device)
+    assert tuple(frames_out.shape) == (B, H, W, 3) and frames_out.dtype == torch.uint8
+    assert tuple(masks_out.shape) == (B, H, W) and masks_out.dtype == torch.float32
+    check(lib.kd6d_cache_gather_frames(_ptr(frames), _ptr(masks), n, H, W, _ptr(index), B, _ptr(frames_out),
+                                       _ptr(masks_out), _stream()), "kd6d_cache_gather_frames")
+    return frames_out, masks_out
+
+
+def cache_gather_targets(table_f, table_i, kp3d, index, bbox_trans, flat_f=None, flat_i=None):
+    """Annotation table rows `index` + the crop launch's bbox_trans (B,2,3) -> (flat_f, flat_i) of a PackedTargets."""
+    n = int(table_f.shape[0])
+    assert table_f.dtype == torch.float32 and tuple(table_f.shape) == (n, _lib.CACHE_ROW_F)
+    assert table_i.dtype == torch.int32 and tuple(table_i.shape) == (n, _lib.CACHE_ROW_I)
+    assert kp3d.dtype == torch.float32 and index.dtype == torch.int32
+    B = int(index.numel())
+    assert bbox_trans.dtype == torch.float32 and bbox_trans.numel() == B * 6
+    nf, ni = cache_target_sizes(B, int(kp3d.numel()))
+    if flat_f is None:
+        flat_f = torch.empty(nf, dtype=torch.float32, device=table_f.device)
+    if flat_i is None:
+        flat_i = torch.empty(ni, dtype=torch.int32, device=table_f.device)
+    assert flat_f.numel() == nf and flat_i.numel() == ni
+    check(lib.kd6d_cache_gather_targets(_ptr(table_f), _ptr(table_i), _ptr(kp3d), int(kp3d.numel()), n, _ptr(index), B,
+                                        _ptr(bbox_trans), _ptr(flat_f), _ptr(flat_i), _stream()),
+          "kd6d_cache_gather_targets")
+    return flat_f, flat_i

@@ -3,6 +3,7 @@ checkpoint without starting a training run.
 
     python test.py --config_file ./configs/ape.yaml --backbone darknet_tiny_h --weight_file outputs/ape/kd/final.pth \
         --working_dir outputs/ape/test/ --pnp_solver device --eval_scorer device [--test_file list.txt | --synthetic]
+        [--frame_cache device]
 
 Builds the network named by --backbone, loads --weight_file (a bare state dict or one under a 'model' key, loosely by
 name as the reference does; says whether weights were loaded or are random), builds the valid-style loader over
@@ -78,7 +79,8 @@ def main(argv=None):
         from train_kd import synthetic_valid_loader
         loader, meshes = synthetic_valid_loader(cfg, device)
     else:
-        loader = build_test_dataset(cfg, device)
+        loader = build_test_dataset(cfg, device, frame_cache=cfg["RUNTIME"].get("FRAME_CACHE", "off"),
+                                    frame_cache_gb=cfg["RUNTIME"].get("FRAME_CACHE_GB", 64.))
         meshes = dataset_meshes(loader)
 
     preds = {}
