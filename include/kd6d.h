@@ -533,6 +533,29 @@ int kd6d_teacher_pnp_gate(const float* cls, int n_cls, float threshold, const in
                           const float* t_kp, int cap, int batch, const float* kp3d, int n_class_rows, const float* K,
                           float reproj_err, int iters, uint64_t seed, float* workspace, int64_t workspace_floats,
                           void* stream);
+/* ---- pose remap of the augmentation chain on the device (csrc/pnp.hip; added under ABI 11, a new symbol only):
+ * kd6d/libs/pnp.py's remap_pose for every instance of a batch, chained twice as kd6d/libs/augment.py::draw_params
+ * chains it (Resize, then RandomShiftScaleRotate).  ONE LANE PER INSTANCE.  Instance i belongs to image inst_img[i]
+ * (n_inst) and has class inst_cls[i] (n_inst); src_K (n_images, 9), src_R (n_inst, 9) and src_T (n_inst, 3) are DOUBLE
+ * (the annotation files are read in double; rounding T ~ 1000 mm to fp32 first would by itself move a corner by about
+ * 3e-5 px); box (n_class, 8, 3) fp32 object-space corners; dst_K_host (9) double, read before the call
+ * returns; M_resize and M_ssr (n_images, 6) double: the first two rows of the homographies, the third is (0, 0, 1);
+ * M_ssr may be NULL.
+ * A stage (source K, M, source pose (R, T)): pts_k = M (K (R X_k + T)), xy_k = pts_k.xy / (pts_k.z + 1e-8) for the 8
+ * corners X_k of the instance's class; DLT of the 8 correspondences on dst_K's normalised coordinates, then 20
+ * Gauss-Newton steps on (rotation vector, t) (the solver of kd6d_pnp_ransac with one observation per corner; dst_K
+ * enters it rounded to fp32 like every K of that solver).  Stage 1 = (src_K, M_resize, (src_R, src_T)); stage 2 =
+ * (dst_K, M_ssr, stage 1's result rounded to fp32), or a copy of stage 1 when M_ssr is NULL.
+ * pose_out (n_inst, 2, 12) fp32 = per stage {R (9), T (3)}, ok_out (n_inst, 2).  A stage that finds no pose (the DLT
+ * fails, a non-finite value, a box with fewer than 6 distinct corners) has ok = 0 and returns its SOURCE pose rounded to
+ * fp32 -- remap_pose's (srcR, srcT, -1) -- and the chain goes on from it.  An inst_img outside [0, n_images) or an
+ * inst_cls outside [0, n_class) is never dereferenced: ok = 0 and a zero pose for both stages.  No LDS, no atomics, no
+ * cross-lane arithmetic: a lane's result is a pure function of its own instance -- bitwise reproducible, independent
+ * of the instance's position and of the batch around it.  Rows from n_inst on are not written. */
+int kd6d_pose_remap(int n_inst, int n_images, int n_class, const int32_t* inst_img, const int32_t* inst_cls,
+                    const double* src_K, const double* src_R, const double* src_T, const float* box,
+                    const double* dst_K_host, const double* M_resize, const double* M_ssr, float* pose_out,
+                    int32_t* ok_out, void* stream);
 /* ---- pose errors of evaluation on the device (csrc/pose_err.hip; added under ABI 11, a new symbol only):
  * libs/utils.py::compute_pose_diff for n_problems (ground truth, prediction) pairs in ONE launch, one workgroup per
  * problem.  Problem p scores vcnt[p] (1 ... max_v, max_v <= KD6D_POSE_ERR_MAX_V = the reference's subsample size)

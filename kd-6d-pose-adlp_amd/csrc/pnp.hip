@@ -12,6 +12,8 @@
 //                    and, with >= 6 points on >= 6 corners, runs 6 more steps and counts again.  It writes
 //                    {count, R, T} to its own workspace slot.
 //   pnp_pick_kernel  one wave per problem: the winner is (count desc, h asc); ok = count >= 6 and R, T finite.
+//   pose_remap_kernel (kd6d_pose_remap, further down): ONE LANE PER INSTANCE, the same DLT and Gauss-Newton on one clean
+//                    observation per corner -- the two pose remaps of the augmentation chain, kd6d/libs/pnp.py's remap_pose.
 //
 // Every correspondence of corner k is scored against the same projected corner, so a consensus set reduces to eight
 // per-corner sums (count, sum of residuals, their second moments): the Gauss-Newton normal equations and the DLT's
@@ -546,6 +548,103 @@ __global__ __launch_bounds__(64) void pnp_pick_kernel(const int32_t* cnt, int it
   for (int i = 0; i < 3; ++i) T[(size_t)p * 3 + i] = good ? r[9 + i] : 0.f;
 }
 
+// ---- pose remap of the augmentation chain (kd6d_pose_remap) ----------------------------------------------------------
+// kd6d/libs/pnp.py's remap_pose, chained as kd6d/libs/augment.py::draw_params chains it: ONE LANE PER INSTANCE, the
+// solver above with one observation per corner (n_k = 1, the sums are the observation itself).
+struct RemapArgs {
+  int n_inst, n_images, n_class;
+  const int32_t* inst_img;
+  const int32_t* inst_cls;
+  const double* src_K;       // (n_images, 9)
+  const double* src_R;       // (n_inst, 9)
+  const double* src_T;       // (n_inst, 3)
+  const float* box;          // (n_class, 8, 3)
+  double dst_K[9];
+  const double* M_resize;    // (n_images, 6)
+  const double* M_ssr;       // (n_images, 6) or nullptr
+  float* pose_out;           // (n_inst, 2, 12)
+  int32_t* ok_out;           // (n_inst, 2)
+};
+
+// one stage: where (R, T) seen through Ks and mapped by M puts the corners -> the pose that puts them there through P.K
+__device__ bool remap_stage(const Problem& P, const double* Ks, const double* M, const double* R, const double* T,
+                            Pose& out) {
+  double n8[8], sx[8], sy[8], sr[8], su[8], sv[8];
+  bool fin = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const double X0 = P.X[k][0], X1 = P.X[k][1], X2 = P.X[k][2];
+    const double c0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + T[0];
+    const double c1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + T[1];
+    const double c2 = R[6] * X0 + R[7] * X1 + R[8] * X2 + T[2];
+    const double p0 = Ks[0] * c0 + Ks[1] * c1 + Ks[2] * c2;
+    const double p1 = Ks[3] * c0 + Ks[4] * c1 + Ks[5] * c2;
+    const double p2 = Ks[6] * c0 + Ks[7] * c1 + Ks[8] * c2;
+    const double q0 = M[0] * p0 + M[1] * p1 + M[2] * p2, q1 = M[3] * p0 + M[4] * p1 + M[5] * p2;
+    const double u = q0 / (p2 + 1e-8), v = q1 / (p2 + 1e-8);
+    fin = fin && isfinite(u) && isfinite(v);
+    const double x = P.a[0] * u + P.a[1] * v + P.a[2], y = P.b[0] * u + P.b[1] * v + P.b[2];
+    n8[k] = 1.0; sx[k] = x; sy[k] = y; sr[k] = x * x + y * y;
+    su[k] = u; sv[k] = v;
+  }
+  if (!fin || !dlt(P, n8, sx, sy, sr, out)) return false;
+  gauss_newton(P, n8, su, sv, out, 20);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) fin = fin && isfinite(out.R[i]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) fin = fin && isfinite(out.t[i]);
+  return fin;
+}
+
+__global__ __launch_bounds__(64) void pose_remap_kernel(RemapArgs a) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= a.n_inst) return;
+  float* out = a.pose_out + (size_t)i * 24;
+  int32_t* ok = a.ok_out + (size_t)i * 2;
+  const int img = a.inst_img[i], cls = a.inst_cls[i];
+  if (img < 0 || img >= a.n_images || cls < 0 || cls >= a.n_class) {
+    for (int j = 0; j < 24; ++j) out[j] = 0.f;
+    ok[0] = ok[1] = 0;
+    return;
+  }
+  float Kd[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) Kd[j] = (float)a.dst_K[j];
+  Problem P;
+  const bool valid = load_problem(P, nullptr, 0, a.box + (size_t)cls * 24, Kd);
+  double R[9], T[3], Ks[9], M[6];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    R[j] = a.src_R[(size_t)i * 9 + j];
+    Ks[j] = a.src_K[(size_t)img * 9 + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) T[j] = a.src_T[(size_t)i * 3 + j];
+  int good = 0;
+#pragma unroll 1                               // one copy of the solver
+  for (int stage = 0; stage < 2; ++stage) {
+    const double* Ms = stage == 0 ? a.M_resize : a.M_ssr;
+    if (Ms) {                                  // stage 2 without M_ssr: a copy of stage 1 (R, T and good as they are)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) M[j] = Ms[(size_t)img * 6 + j];
+      Pose ps;
+      good = valid && remap_stage(P, Ks, M, R, T, ps) ? 1 : 0;
+      // the result (or, without one, the source pose) rounded to fp32: what is written and what the chain goes on from
+#pragma unroll
+      for (int j = 0; j < 9; ++j) R[j] = (double)(float)(good ? ps.R[j] : R[j]);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) T[j] = (double)(float)(good ? ps.t[j] : T[j]);
+#pragma unroll
+      for (int j = 0; j < 9; ++j) Ks[j] = a.dst_K[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 9; ++j) out[stage * 12 + j] = (float)R[j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[stage * 12 + 9 + j] = (float)T[j];
+    ok[stage] = good;
+  }
+}
+
 int launch(const char* name, int n_problems, const HypArgs& a, int32_t* ok, float* R, float* T, int32_t* n_inliers,
            int32_t* t_cnt_out, void* stream) {
   if (n_problems == 0) return KD6D_OK;
@@ -603,4 +702,24 @@ extern "C" int kd6d_teacher_pnp_gate(const float* cls, int n_cls, float threshol
   a.seed = seed; a.cls = cls; a.t_row = t_row; a.n_cls = n_cls; a.n_class_rows = n_class_rows;
   a.threshold = threshold; a.ws = workspace;
   return launch("kd6d_teacher_pnp_gate", batch, a, nullptr, nullptr, nullptr, nullptr, t_cnt, stream);
+}
+
+extern "C" int kd6d_pose_remap(int n_inst, int n_images, int n_class, const int32_t* inst_img, const int32_t* inst_cls,
+                               const double* src_K, const double* src_R, const double* src_T, const float* box,
+                               const double* dst_K_host, const double* M_resize, const double* M_ssr, float* pose_out,
+                               int32_t* ok_out, void* stream) {
+  KD6D_CHECK_ARG(inst_img && inst_cls && src_K && src_R && src_T && box && dst_K_host && M_resize && pose_out && ok_out,
+                 "kd6d_pose_remap: null pointer");
+  KD6D_CHECK_ARG(n_inst > 0 && n_inst <= (1 << 24), "kd6d_pose_remap: n_inst=%d (1 ... %d)", n_inst, 1 << 24);
+  KD6D_CHECK_ARG(n_images > 0, "kd6d_pose_remap: n_images=%d (>= 1)", n_images);
+  KD6D_CHECK_ARG(n_class > 0, "kd6d_pose_remap: n_class=%d (>= 1)", n_class);
+  RemapArgs a = {};
+  a.n_inst = n_inst; a.n_images = n_images; a.n_class = n_class; a.inst_img = inst_img; a.inst_cls = inst_cls;
+  a.src_K = src_K; a.src_R = src_R; a.src_T = src_T; a.box = box; a.M_resize = M_resize; a.M_ssr = M_ssr;
+  a.pose_out = pose_out; a.ok_out = ok_out;
+  for (int j = 0; j < 9; ++j) a.dst_K[j] = dst_K_host[j];
+  hipLaunchKernelGGL(pose_remap_kernel, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  KD6D_CHECK_LAUNCH("kd6d_pose_remap");
+  return KD6D_OK;
 }

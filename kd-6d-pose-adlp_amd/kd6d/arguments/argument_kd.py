@@ -3,7 +3,7 @@
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
---synthetic_instances, --frame_cache, --frame_cache_gb; yaml files may name a `_BASE_` file.
+--synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap; yaml files may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -59,6 +59,11 @@ def get_argparser():
     p.add_argument("--augment", action="store_true",
                    help="real data: run the reference's train transform chain (Resize, occlusion, shift-scale-rotate, HSV, "
                         "blur, noise, grey, remove_invalids, symmetry handling) on the GPU front-end (kd6d/libs/augment.py)")
+    p.add_argument("--aug_pose_remap", type=str, default="host", choices=["host", "device"],
+                   help="--augment: where the two pose remaps of an item (Resize, shift-scale-rotate) are solved: host = "
+                        "numpy, two solves per instance when the item is drawn (kd6d/libs/pnp.py); device = HIP "
+                        "(csrc/pnp.hip), every instance of a batch in one launch of the augmentation front-end, read back "
+                        "with its area table")
     p.add_argument("--skip_teacher_eval", action="store_true")
     p.add_argument("--launch", type=str, default="graph", choices=["graph", "pipeline", "eager"],
                    help="graph: replay the captured step (hipGraph); pipeline: also overlap the teacher forward of "
@@ -126,6 +131,17 @@ def frame_cache_runtime(args):
     return dict(FRAME_CACHE=mode, FRAME_CACHE_GB=float(getattr(args, "frame_cache_gb", 64.)))
 
 
+AUG_POSE_REMAP_ERROR = "--aug_pose_remap device needs --augment: without it no pose is remapped"
+
+
+def aug_pose_remap_runtime(args):
+    """-> RUNTIME.AUG_POSE_REMAP; refuses --aug_pose_remap device without --augment."""
+    mode = getattr(args, "aug_pose_remap", "host")
+    if mode == "device" and not bool(getattr(args, "augment", False)):
+        raise ValueError(AUG_POSE_REMAP_ERROR)
+    return mode
+
+
 def load_yaml(path):
     """yaml -> dict.  A top-level `_BASE_: other.yaml` (path relative to the file; additive key of this build) is
     loaded first and the file's own sections are merged over it key by key."""
@@ -164,6 +180,7 @@ def build_cfgs(args):
     cfg["RUNTIME"]["WORKING_DIR"] = args.working_dir
     cfg["RUNTIME"]["SYNTHETIC"] = bool(args.synthetic)
     cfg["RUNTIME"]["AUGMENT"] = bool(getattr(args, "augment", False))
+    cfg["RUNTIME"]["AUG_POSE_REMAP"] = aug_pose_remap_runtime(args)
     cfg["RUNTIME"].update(frame_cache_runtime(args))
     cfg["RUNTIME"]["SKIP_TEACHER_EVAL"] = bool(args.skip_teacher_eval)
     cfg["RUNTIME"]["LAUNCH"] = args.launch

@@ -18,6 +18,11 @@ Split of the work:
     maps them with random.uniform's own formula a + (b - a) u.
   * `AugmentFront.run` (DziLoader, GPU): the pixel work in csrc/augment.hip, one readback of the (B, n) area table
     (waited on with an event of the front-end's stream), the drop / relabel decision, symmetry handling.
+  * RUNTIME.AUG_POSE_REMAP = "device" (train_kd.py --aug_pose_remap device): `draw_params` solves nothing -- it records
+    the source poses in double (`pose_src`) and draws exactly what it draws otherwise -- and `AugmentFront.run` starts
+    with ONE kd6d_pose_remap launch (csrc/pnp.hip: one lane per instance, both remaps chained) whose result comes back
+    with the area table, behind the same single wait.  The poses agree with the host solver's to well under 1e-3
+    projected px (profiles/aug_pose_remap.md); frames and masks do not depend on them.
 
 Deviations from the reference:
   * the remap of an instance uses the 8 box corners of its CLASS (keypoints_3d[class_ids[i]]); PoseAnnot.transform
@@ -36,6 +41,7 @@ from .._lib import AUG_MAX_ID, MAX_GT
 from .pnp import remap_pose
 
 MIN_AREA = 10
+POSE_REMAP_MODES = ("host", "device")
 
 
 class AugConfig:
@@ -60,6 +66,9 @@ class AugConfig:
         self.noise = float(s.get("AUGMENTATION_Noise", 0) or 0)
         self.gray = bool(s.get("AUGMENTATION_Grayscalize", False))
         self.symmetry_types = cfg["DATASETS"].get("SYMMETRY_TYPES") or {}
+        self.pose_remap = (cfg.get("RUNTIME") or {}).get("AUG_POSE_REMAP", "host")
+        if self.pose_remap not in POSE_REMAP_MODES:
+            raise ValueError("RUNTIME.AUG_POSE_REMAP must be one of %s (got %r)" % (POSE_REMAP_MODES, self.pose_remap))
 
     # the guards of transform.py
     @property
@@ -130,21 +139,31 @@ def remap_poses(K, class_ids, rotations, translations, bbox_3d, dst_K, M):
 
 
 def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random):
-    """Everything random of one item, in the chain's order, and the two pose remaps.  -> dict."""
+    """Everything random of one item, in the chain's order, and the two pose remaps.  -> dict.
+    ac.pose_remap == "device": no remap is solved here; the item carries its source poses in double (`pose_src`) for
+    kd6d_pose_remap instead of R_resize / T_resize / R / T.  The draws are the same, in the same order."""
     n = len(class_ids)
     if n > AUG_MAX_ID:
         raise ValueError("--augment handles at most %d instances per frame (got %d)" % (AUG_MAX_ID, n))
+    on_device = ac.pose_remap == "device"
     p = {}
     Mr = resize_matrix(ac.K, K)
     p["M_resize"] = Mr[:2].copy()
-    p["R_resize"], p["T_resize"] = remap_poses(K, class_ids, rotations, translations, bbox_3d, ac.K, Mr)
+    if on_device:
+        p["pose_src"] = {"K": np.asarray(K, np.float64).reshape(3, 3).copy(),
+                         "class_ids": np.asarray(class_ids, np.int64).reshape(n),
+                         "rotations": np.asarray(rotations, np.float64).reshape(n, 3, 3).copy(),
+                         "translations": np.asarray(translations, np.float64).reshape(n, 3).copy()}
+    else:
+        p["R_resize"], p["T_resize"] = remap_poses(K, class_ids, rotations, translations, bbox_3d, ac.K, Mr)
     if ac.occlusion_on:
         p["occl_u"] = np.array([[rng.random() for _ in range(5)] for _ in range(MAX_GT)], np.float64)
     if ac.ssr_on:
         Ms = shift_scale_rotate_matrix(ac.shift, ac.scale, ac.rotation, ac.width, ac.height, rng)
         p["M_ssr"] = Ms[:2].astype(np.float64)
-        p["R"], p["T"] = remap_poses(ac.K, class_ids, p["R_resize"], p["T_resize"], bbox_3d, ac.K, Ms)
-    else:
+        if not on_device:
+            p["R"], p["T"] = remap_poses(ac.K, class_ids, p["R_resize"], p["T_resize"], bbox_3d, ac.K, Ms)
+    elif not on_device:
         p["R"], p["T"] = p["R_resize"], p["T_resize"]
     if ac.hsv_on:
         p["hsv"] = np.array([rng.uniform(-1, 1) * r + 1 for r in ac.hsv], np.float32)
@@ -158,11 +177,25 @@ def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random):
 
 
 def collate_params(ps):
-    """list of draw_params dicts -> one dict of stacked arrays (per-instance poses stay lists)."""
+    """list of draw_params dicts -> one dict of stacked arrays (per-instance poses stay lists).  Items drawn for the
+    device remap: `pose_src` = the instances of the batch, image after image, in kd6d_pose_remap's arrays -- inst_img,
+    inst_cls (n_inst,) int32, src_K (B, 9), src_R (n_inst, 9), src_T (n_inst, 3) float64 -- and start (B + 1,): image
+    b owns instances start[b] ... start[b + 1] - 1."""
     out = {"M_resize": np.stack([p["M_resize"] for p in ps]), "n": np.array([p["n"] for p in ps], np.int32),
            "key": np.array([p["key"] for p in ps], np.uint64)}
-    for k in ("R_resize", "T_resize", "R", "T"):
-        out[k] = [p[k] for p in ps]
+    if "pose_src" in ps[0]:
+        src = [p["pose_src"] for p in ps]
+        cnt = [len(q["class_ids"]) for q in src]
+        out["pose_src"] = {
+            "inst_img": np.repeat(np.arange(len(ps), dtype=np.int32), cnt),
+            "inst_cls": np.concatenate([q["class_ids"] for q in src]).astype(np.int32),
+            "src_K": np.stack([q["K"].reshape(9) for q in src]).astype(np.float64),
+            "src_R": np.concatenate([q["rotations"].reshape(-1, 9) for q in src]).astype(np.float64),
+            "src_T": np.concatenate([q["translations"].reshape(-1, 3) for q in src]).astype(np.float64),
+            "start": np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)}
+    else:
+        for k in ("R_resize", "T_resize", "R", "T"):
+            out[k] = [p[k] for p in ps]
     if "occl_u" in ps[0]:
         out["occl_u"] = np.stack([p["occl_u"] for p in ps])
     if "M_ssr" in ps[0]:
@@ -265,6 +298,63 @@ class AugmentFront:
 
     def __init__(self, ac, device):
         self.ac, self.device = ac, device
+        self._box = None                     # (host copy, device copy) of the last box table kd6d_pose_remap read
+
+    def _box_table(self, targets):
+        """The (n_class, 8, 3) box corners the batch's class ids index, on the device (uploaded when they change).
+        Every image of a batch must carry the same table."""
+        kp = targets[0].keypoints_3d
+        for t in targets[1:]:
+            if t.keypoints_3d is not kp and not (t.keypoints_3d.shape == kp.shape and torch.equal(t.keypoints_3d, kp)):
+                raise ValueError("--aug_pose_remap device needs one 3D-box table per batch: the images of this batch "
+                                 "carry different ones")
+        kp = kp.detach().to("cpu", torch.float32).reshape(-1, 8, 3)
+        if self._box is None or self._box[0].shape != kp.shape or not torch.equal(self._box[0], kp):
+            self._box = (kp.clone(), kp.to(self.device).contiguous())
+        return self._box[1]
+
+    def _launch_pose_remap(self, targets, params):
+        """kd6d_pose_remap over the batch's instances on the current stream -> (pose, ok) in pinned memory (valid after
+        the caller's wait), or None for a batch without instances."""
+        from .. import ops
+        src = params["pose_src"]
+        n = int(src["inst_img"].shape[0])
+        if n == 0:
+            return None
+        B = len(targets)
+        box = self._box_table(targets)
+        Ms = params["M_ssr"] if self.ac.ssr_on and "M_ssr" in params else None
+        parts = [src["src_K"].reshape(-1), src["src_R"].reshape(-1), src["src_T"].reshape(-1),
+                 np.asarray(params["M_resize"], np.float64).reshape(-1)]
+        if Ms is not None:
+            parts.append(np.asarray(Ms, np.float64).reshape(-1))
+        f = _dev(np.concatenate(parts).astype(np.float64), torch.float64, self.device)
+        i = _dev(np.concatenate([src["inst_img"], src["inst_cls"]]).astype(np.int32), torch.int32, self.device)
+        cut = np.cumsum([0, B * 9, n * 9, n * 3, B * 6, B * 6])
+        pose, ok = ops.pose_remap(i[:n], i[n:], f[cut[0]:cut[1]], f[cut[1]:cut[2]], f[cut[2]:cut[3]], box, self.ac.K,
+                                  f[cut[3]:cut[4]], f[cut[4]:cut[5]] if Ms is not None else None)
+        hp = torch.empty(pose.shape, dtype=torch.float32, pin_memory=True)
+        ho = torch.empty(ok.shape, dtype=torch.int32, pin_memory=True)
+        hp.copy_(pose, non_blocking=True)
+        ho.copy_(ok, non_blocking=True)
+        return hp, ho
+
+    @staticmethod
+    def _fill_poses(params, remap, ssr):
+        """R_resize / T_resize / R / T of `params`, per image, from kd6d_pose_remap's readback (remap_poses' shapes)."""
+        start = params["pose_src"]["start"]
+        B = len(start) - 1
+        if remap is None:
+            pose, ok = np.zeros((0, 2, 12), np.float32), np.zeros((0, 2), np.int32)
+        else:
+            pose, ok = remap[0].numpy(), remap[1].numpy()
+        # one line per remap the host chain would have run: without an SSR stage, stage 2 only repeats stage 1's flag
+        stages = 2 if ssr else 1
+        for _ in range(int((ok[:, :stages] == 0).sum())):
+            print("Error in pose remapping!")
+        for stage, (kr, kt) in enumerate((("R_resize", "T_resize"), ("R", "T"))):
+            params[kr] = [pose[start[b]:start[b + 1], stage, :9].reshape(-1, 3, 3).copy() for b in range(B)]
+            params[kt] = [pose[start[b]:start[b + 1], stage, 9:].reshape(-1, 3, 1).copy() for b in range(B)]
 
     def run(self, frames, masks, targets, params):
         """frames (B,H,W,3) uint8 / masks (B,H,W) float32 on the device, the items' original PoseAnnots, collated
@@ -274,6 +364,8 @@ class AugmentFront:
         B, H, W, _ = frames.shape
         key = batch_key(params["key"])
         size = (ac.height, ac.width)
+        # 0 the pose remaps of the whole batch (--aug_pose_remap device): first on the stream, read back with the areas
+        remap = self._launch_pose_remap(targets, params) if "pose_src" in params else None
         # 1 Resize
         if (H, W) == size and all(is_identity_warp(np.vstack([m, [0, 0, 1]]), W, H) for m in params["M_resize"]):
             resized, resized_m = frames, masks
@@ -307,6 +399,8 @@ class AugmentFront:
         ev = torch.cuda.Event()
         ev.record()
         ev.synchronize()
+        if "pose_src" in params:
+            self._fill_poses(params, remap, self.ac.ssr_on and "M_ssr" in params)
         area = host[:, :, 0].numpy()
         lut = np.zeros((B, max_id + 1), np.float32)
         out = []

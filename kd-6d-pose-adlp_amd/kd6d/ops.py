@@ -643,6 +643,31 @@ def teacher_pnp_gate(cls, n_cls, threshold, t_row, t_cnt, t_kp, cap, kp3d, K, re
           "kd6d_teacher_pnp_gate")
 
 
+def pose_remap(inst_img, inst_cls, src_K, src_R, src_T, box, dst_K, M_resize, M_ssr=None, pose_out=None, ok_out=None):
+    """The two pose remaps of the augmentation chain for every instance of a batch in one launch (csrc/pnp.hip,
+    kd6d/libs/pnp.py::remap_pose chained as augment.draw_params chains it).  inst_img, inst_cls (n,) int32; src_K
+    (n_images, 3, 3), src_R (n, 3, 3), src_T (n, 3) float64; box (n_class, 8, 3) float32; M_resize, M_ssr (n_images, 2, 3)
+    float64 (M_ssr None: no second stage) -- device tensors; dst_K: 9 numbers on the host.
+    -> pose (n, 2, 12) fp32 = per stage {R 9, T 3}, ok (n, 2) int32 (device tensors, no synchronisation)."""
+    n = inst_img.numel()
+    dev = box.device
+    assert inst_img.dtype == torch.int32 and inst_cls.dtype == torch.int32 and inst_cls.numel() == n
+    assert box.dtype == torch.float32 and box.dim() == 3 and tuple(box.shape[1:]) == (8, 3)
+    n_images, n_class = src_K.numel() // 9, box.shape[0]
+    for t, m in ((src_K, n_images * 9), (src_R, n * 9), (src_T, n * 3), (M_resize, n_images * 6), (M_ssr, n_images * 6)):
+        assert t is None or (t.dtype == torch.float64 and t.numel() == m), "pose_remap: float64 (%d) expected" % m
+    pose = torch.empty(n, 2, 12, dtype=torch.float32, device=dev) if pose_out is None else pose_out
+    ok = torch.empty(n, 2, dtype=torch.int32, device=dev) if ok_out is None else ok_out
+    assert pose.dtype == torch.float32 and pose.numel() >= n * 24 and ok.dtype == torch.int32 and ok.numel() >= n * 2
+    if n == 0:
+        return pose, ok
+    kd = (ctypes.c_double * 9)(*[float(v) for v in (dst_K.reshape(-1).tolist() if hasattr(dst_K, "reshape") else dst_K)])
+    check(lib.kd6d_pose_remap(n, n_images, n_class, _ptr(inst_img), _ptr(inst_cls), _ptr(src_K), _ptr(src_R), _ptr(src_T),
+                              _ptr(box), kd, _ptr(M_resize), _ptr(M_ssr), _ptr(pose), _ptr(ok), _stream()),
+          "kd6d_pose_remap")
+    return pose, ok
+
+
 def pose_errors(verts, voff, vcnt, vidx, K, Rg, Tg, Rp, Tp, sym, max_v=None, want_nn=False, validate=True):
     """Mean 3D / 2D-reprojection error of P (ground truth, prediction) pairs in one launch (csrc/pose_err.hip,
     evaluate.py::compute_pose_diff).  verts (Nv, 3) fp32 pool; voff, vcnt, sym (P,) int32; vidx (P, max_v) int32 relative

@@ -7,6 +7,8 @@ figure is per launch, launch overhead amortised as in a replayed training step):
   * eval:  kd6d_pnp_ransac on 16 x MAX_GT = 64 problems of 32 cells each (1-px votes, 20 % 60-px outliers), iters 300;
   * gate:  kd6d_teacher_pnp_gate at B = 16 and B = 48 (the grouped teacher of --teacher_group 3), 10 cells per image
            (POSITIVE_NUM) and 32 cells per image, iters 300.
+  * remap: kd6d_pose_remap (the two chained pose remaps of --augment, one lane per instance) at 16 and 64 instances,
+           Resize from another camera, then shift-scale-rotate at the ape.yaml limits.
 Host: wall time per problem of solve_pnp_ransac on the first `host_problems` eval problems (same inputs).
 """
 import argparse
@@ -116,6 +118,31 @@ def main():
                                 "us_per_16_images": round(us * 16 / B, 1), "kept": kept})
             print("gate  B=%d, %d cells: %.1f us per launch (%.1f us per 16 images), %d/%d kept"
                   % (B, cells, us, us * 16 / B, kept, B))
+    # pose remap of the augmentation chain: n_inst instances, one per image
+    res["remap"] = []
+    for n in (16, 64):
+        src_K = K.copy(); src_K[0, 0] *= 0.9; src_K[1, 1] *= 0.9; src_K[0, 2] += 7.0; src_K[1, 2] -= 5.0
+        Rs, Ts, Mr, Ms = [], [], [], []
+        for _ in range(n):
+            q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+            Rs.append(q * np.linalg.det(q))
+            Ts.append([rng.normal(0, 60), rng.normal(0, 40), 900 + rng.normal(0, 80)])
+            Mr.append((K @ np.linalg.inv(src_K))[:2])
+            a_, sc = np.deg2rad(rng.uniform(-10, 10)), 1 + rng.uniform(-0.05, 0.05)
+            al, be = np.cos(a_) * sc, np.sin(a_) * sc
+            Ms.append([[al, be, (1 - al) * 320 - be * 240 + rng.uniform(-32, 32)],
+                       [-be, al, be * 320 + (1 - al) * 240 + rng.uniform(-24, 24)]])
+        f64 = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)  # noqa: E731
+        img = torch.arange(n, dtype=torch.int32, device=dev)
+        cls0 = torch.zeros(n, dtype=torch.int32, device=dev)
+        bx = torch.from_numpy(box()[None].astype(np.float32)).to(dev)
+        args_ = (img, cls0, f64(np.stack([src_K] * n)), f64(Rs), f64(Ts), bx, K, f64(Mr), f64(Ms))
+        pose_o = torch.empty(n, 2, 12, device=dev)
+        ok_o = torch.empty(n, 2, dtype=torch.int32, device=dev)
+        us = graph_time(lambda: ops.pose_remap(*args_, pose_out=pose_o, ok_out=ok_o), a.reps)
+        torch.cuda.synchronize()
+        res["remap"].append({"n_inst": n, "us_per_launch": round(us, 1), "solved": int(ok_o.sum())})
+        print("remap %d instances: %.1f us per launch, %d/%d stages solved" % (n, us, int(ok_o.sum()), 2 * n))
     # host solver on the same eval problems
     n = min(a.host_problems, P)
     t0 = time.perf_counter()
