@@ -406,7 +406,9 @@ int kd6d_barrier_timeouts(void);
  * groups): skip the reduction pass; bit 1 (KD6D_GN_WS_ZEROED) -- the caller zeroed stats (fwd, when not
  * ready) / gsum_ws (bwd) itself (e.g. one memset of a whole scratch arena per step): skip the memset node.
  * dgamma / dbeta (backward, optional): PLANAR gradient accumulators with stride acc_hi_stride (see "reproducible
- * reductions").  Requires C/groups >= granule/2 (a 16-B granule spans <= 2 groups). */
+ * reductions").  Requires C/groups >= granule/2 (a 16-B granule spans <= 2 groups).
+ * kd6d_gn_relu_bwd (and _pair) accept C <= 512 only -- the kernels keep 32*C bytes of per-channel accumulators in
+ * the 16 KB of LDS they are launched with; a wider tensor is refused with KD6D_ERR_ARG. */
 #define KD6D_GN_STATS_READY 1
 #define KD6D_GN_WS_ZEROED 2
 int kd6d_gn_relu_fwd(int dtype, int x_f32, const void* x, void* y, const int32_t* level_hw_host, int nseg, int batch,

@@ -12,10 +12,11 @@
 #include "kd6d_barrier.h"
 #include "kd6d_common.h"
 #include "kd6d_det.h"
+#include "norm_plan.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace kd6d_norm;      // kThreads, kFlushLdsBytes, the hold counts: one definition for kernels and launch rules
 using kd6d_detail::det_add_lds;
 using kd6d_detail::det_add_words;
 using kd6d_detail::det_add_words_performed;
@@ -42,8 +43,7 @@ __device__ __forceinline__ float row_ror_add(float v) {
 // LDS atomics: at most 16 partial sums per channel (narrow tensors: the lanes of a 16-lane row that own the same channel
 // granule are summed with DPP rotations first), one fixed-point conversion per channel and workgroup.
 // Dynamic LDS: kFlushLdsBytes.  PLANAR: out[a] is the lo plane of a gradient-bucket accumulator array (hi words at
-// + hi_off, no replica rows).
-constexpr int kFlushLdsBytes = 16384;      // 256 threads x NACC * EG (<= 16) floats
+// + hi_off, no replica rows).  LDS bytes used: norm_plan.h, flush_lds_bytes.
 template <int NACC, int EG, int E, bool PERFORMED = false, bool PLANAR = false>
 __device__ __forceinline__ void block_channel_flush(float (&acc)[NACC][EG], int C, int cg,
                                                     acc_t* const* out, int replicas = 1, long long hi_off = 0) {
@@ -571,8 +571,6 @@ __global__ __launch_bounds__(kThreads) void bn_pool_bwd_apply_kernel(
 // and a step has one such kernel in flight at a time, so the barrier completes; group_barrier's spin limit is the
 // safety net.  Larger tensors take the reduce + apply pair.
 // ---------------------------------------------------------------------------
-constexpr int kBnHold = 4;
-constexpr int kBnOnepassBlocks = 512;
 
 // totals of the replica rows -> tot[2C] (LDS floats), read with device-scope atomic loads (see group_barrier); the
 // words of the rows are added as integers (exact) and converted once
@@ -691,7 +689,6 @@ __global__ __launch_bounds__(kThreads, 3) void bn_bwd_onepass_kernel(
 }
 
 // the pooled variant: <= kPoolHold windows per thread (xhat of the four taps, the pooled gradient, the argmax)
-constexpr int kPoolHold = 2;
 template <typename T, typename TX>
 __global__ __launch_bounds__(kThreads, 3) void bn_pool_bwd_onepass_kernel(
     const TX* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, int items, int per_thread, int H, int W,
@@ -781,9 +778,6 @@ __global__ __launch_bounds__(kThreads, 3) void bn_pool_bwd_onepass_kernel(
 // workgroups, so a 32x32 level is reduced by 16 workgroups instead of one); consumers derive
 // mean = s/n, rstd = rsqrt(max(q/n - mean^2, 0) + eps) with n = H*W*C/G.
 // ---------------------------------------------------------------------------
-// rows of one (level, sample) handled by a reduction workgroup (GnGeom::chunk_rows)
-int gn_chunk_rows() { return 128; }
-
 struct GnGeom {
   int nseg, batch, C, G;
   int row0[KD6D_MAX_SEG];
@@ -1045,7 +1039,6 @@ __global__ __launch_bounds__(kThreads) void gn_relu_bwd_reduce_kernel(
 // hw / chunk_rows of them, consecutive block ids -- have done the same, and finishes dx from the registers: x and
 // dz are read once instead of twice and the second launch goes.  Siblings are dispatched in order and the largest
 // group is far smaller than the number of resident workgroups, so the wait always ends.
-constexpr int kGnHold = 8;
 template <typename T, typename TX>
 __device__ __forceinline__ void gn_relu_bwd_onepass_body(
     const TX* __restrict__ x, const T* __restrict__ dz, T* __restrict__ dx, const GnGeom& gm, float eps,
@@ -1410,34 +1403,34 @@ __global__ __launch_bounds__(kThreads) void image_to_nhwc_kernel(const float* __
   }
 }
 
-// Every workgroup of a per-channel reduction ends with one atomic per channel, and same-address atomics
-// retire serially, ~27 ns each (measured: time grows linearly with the workgroup count, 512 -> 2048 = 18 -> 55 us
-// on a 17-MB tensor).  colstats' plain load loop tolerates long per-thread walks, so it is capped at 128
-// workgroups; the BatchNorm backward reduction is latency-bound per thread (8 granules at most) and keeps 512.
-constexpr int kColstatsCap = 128;
-constexpr int kBnBwdReduceCap = 512;
+// Host launchers.  The rules -- accepted channel counts, grids, LDS bytes, the one-launch decisions, the GN backward
+// workspace -- are norm_plan.h's; here they meet the argument checks and the kernels.  Every argument check of an entry
+// point comes before its first call that can touch a device (occupancy query, kd6d_ctx_timeouts_ptr, memset, launch).
 
-int grid_for(long long work_items) {
-  long long b = (work_items + kThreads - 1) / kThreads;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (int)b;
+// What every launcher derives first: the granule width of the dtype, the 16-B granules of `elems` elements, the stream.
+struct Prep { int eg; long long ngran; hipStream_t st; };
+bool prep(int dtype, long long elems, void* stream, Prep* p) {
+  if (dtype != KD6D_BF16 && dtype != KD6D_F32) return false;
+  p->eg = granule_width(dtype == KD6D_BF16);
+  p->ngran = elems / p->eg;
+  p->st = reinterpret_cast<hipStream_t>(stream);
+  return true;
 }
 
-int check_channels(int dtype, int C, const char* who) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "%s: bad dtype %d", who, dtype);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(C > 0 && C % eg == 0, "%s: C=%d must be a multiple of %d", who, C, eg);
-  const int cgs = C / eg;
-  KD6D_CHECK_ARG(cgs <= 256 && 256 % cgs == 0, "%s: C=%d: C/%d must divide 256", who, C, eg);
+// prep() of a (rows, C) tensor plus the channel rule of the BatchNorm / GroupNorm entry points
+int check_channels(int dtype, int C, long long rows, void* stream, const char* who, Prep* p) {
+  KD6D_CHECK_ARG(prep(dtype, rows * C, stream, p), "%s: bad dtype %d", who, dtype);
+  KD6D_CHECK_ARG(C > 0 && C % p->eg == 0, "%s: C=%d must be a multiple of %d", who, C, p->eg);
+  KD6D_CHECK_ARG(channels_ok(C, p->eg), "%s: C=%d: C/%d must divide 256", who, C, p->eg);
   return KD6D_OK;
 }
 
+// host arithmetic only; the launcher sets gm->timeouts once its checks are through
 bool fill_gn(const int32_t* level_hw, int nseg, int batch, int C, int G, GnGeom* gm, int chunk_rows = 0) {
   if (nseg < 1 || nseg > KD6D_MAX_SEG || batch < 1 || G < 1 || G > 64 || C % G) return false;
   gm->nseg = nseg; gm->batch = batch; gm->C = C; gm->G = G;
   gm->chunk_rows = chunk_rows > 0 ? chunk_rows : gn_chunk_rows();
-  gm->timeouts = kd6d_ctx_timeouts_ptr();
+  gm->timeouts = nullptr;
   int row = 0, blk = 0;
   for (int s = 0; s < KD6D_MAX_SEG; ++s) {
     gm->row0[s] = row;
@@ -1455,35 +1448,25 @@ bool fill_gn(const int32_t* level_hw, int nseg, int batch, int C, int G, GnGeom*
   return true;
 }
 
-// Workgroups of `kernel` the device keeps resident at once (occupancy x CUs); 0 if the query fails.  The kernels
-// with an in-kernel barrier are only launched with grids well inside it.
+// Workgroups of `kernel` the device keeps resident at once (occupancy x CUs); <= 0 if the query fails.  The kernels
+// with an in-kernel barrier are only launched with grids well inside it, and all with kFlushLdsBytes of dynamic LDS.
 template <typename K>
-int resident_workgroups(K kernel, size_t lds) {
+int resident_workgroups(K kernel) {
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, lds) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, kFlushLdsBytes) != hipSuccess) return 0;
   return per_cu * kd6d_device_cu_count();
 }
+enum BarrierKernel { kBnOnepass, kBnPoolOnepass, kGnOnepass };
 template <typename T, typename TX>
-int bn_onepass_capacity(bool pooled) {
-  static const int plain = resident_workgroups(bn_bwd_onepass_kernel<T, TX>, 16384);
-  static const int pool = resident_workgroups(bn_pool_bwd_onepass_kernel<T, TX>, 16384);
-  return pooled ? pool : plain;
+int onepass_capacity(BarrierKernel k) {      // queried once per instantiation
+  static const int v[3] = {resident_workgroups(bn_bwd_onepass_kernel<T, TX>), resident_workgroups(bn_pool_bwd_onepass_kernel<T, TX>),
+                           resident_workgroups(gn_relu_bwd_onepass_kernel<T, TX>)};
+  return v[k];
 }
-template <typename T, typename TX>
-int gn_onepass_capacity() {
-  static const int v = resident_workgroups(gn_relu_bwd_onepass_kernel<T, TX>, 16384);
-  return v;
-}
-// option bn.onepass = 0: the two-launch BN backward even when the caller passes a barrier counter
-bool bn_onepass() { return kd6d_opt(KD6D_OPT_BN_ONEPASS) != 0; }
-// Largest tensor (16-B granules of x) that takes the one-launch BN backward.  Measured on an MI355X
-// (tools/bench_norm.py): up to ~128 workgroups the barrier is cheaper than a second launch (11-13 us against
-// 15 us per layer); at 256-512 workgroups publishing and collecting the partial sums through device-scope
-// returning atomics costs more than re-reading x and dz (27-29 us against 20 us), so those keep the pair.
-// Option bn.onepass_max = <granules> overrides the 65536 (tests drive 512-workgroup grids through it).
-long long bn_onepass_max_granules() { return kd6d_opt(KD6D_OPT_BN_ONEPASS_MAX); }
-// option gn.onepass = 0: the two-launch GN backward (reduce, apply)
-bool gn_onepass() { return kd6d_opt(KD6D_OPT_GN_ONEPASS) != 0; }
+
+acc_t* words(kd6d_acc* a) { return reinterpret_cast<acc_t*>(a); }
+const acc_t* words(const kd6d_acc* a) { return reinterpret_cast<const acc_t*>(a); }
+acc_t* words(int64_t* a) { return reinterpret_cast<acc_t*>(a); }      // planar accumulators
 
 long long gn_rows(const GnGeom& gm) {
   long long r = 0;
@@ -1499,29 +1482,46 @@ int gn_stats_levels(int src_f32, const void* y, const int* row0, const int* hw, 
                     unsigned mask, long long* stats, hipStream_t st);
 }
 
-#define DISPATCH_T(dtype, expr_bf16, expr_f32) \
-  do { if ((dtype) == KD6D_BF16) { expr_bf16; } else { expr_f32; } } while (0)
+// CALL with T_ = the tensors' type / with TX_ = the type x is stored in as well (fp32 pre-normalisation tensor)
+#define DISPATCH_T(dtype, CALL) \
+  do { if ((dtype) == KD6D_BF16) { typedef bf16_t T_; CALL; } else { typedef float T_; CALL; } } while (0)
+#define DISPATCH_TTX(dtype, xf32, CALL)                                        \
+  do {                                                                         \
+    if ((dtype) == KD6D_F32) { typedef float T_; typedef float TX_; CALL; }     \
+    else if (xf32) { typedef bf16_t T_; typedef float TX_; CALL; }              \
+    else { typedef bf16_t T_; typedef bf16_t TX_; CALL; }                       \
+  } while (0)
 
-extern "C" int kd6d_colstats(int dtype, const void* x, int64_t rows, int C, kd6d_acc* sum_acc,
-                             kd6d_acc* sumsq_acc, void* stream) {
-  acc_t* sum = reinterpret_cast<acc_t*>(sum_acc);
-  acc_t* sumsq = reinterpret_cast<acc_t*>(sumsq_acc);
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_colstats: bad dtype %d", dtype);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(C > 0 && C % eg == 0 && C / eg <= kThreads, "kd6d_colstats: C=%d must be a multiple of %d and <= %d",
-                 C, eg, eg * kThreads);
+static int resident(int dtype, int x_f32, BarrierKernel k) {
+  int r = 0;
+  DISPATCH_TTX(dtype, x_f32, r = (onepass_capacity<T_, TX_>(k)));
+  return r;
+}
+
+// the one-launch decision of both BN backwards
+static BnOnepassPlan bn_plan(int dtype, int x_f32, bool pooled, long long items, bool has_counter) {
+  // options bn.onepass = 0: the two-launch backward even with a counter; bn.onepass_max = <granules>: default 65536
+  // (tests drive 512-workgroup grids through it)
+  return bn_onepass_plan(items, pooled ? kBnPooled : kBnPlain, resident(dtype, x_f32, pooled ? kBnPoolOnepass : kBnOnepass),
+                         has_counter, kd6d_opt(KD6D_OPT_BN_ONEPASS) != 0, kd6d_opt(KD6D_OPT_BN_ONEPASS_MAX));
+}
+
+template <bool GRAD>
+static void launch_colstats(int dtype, const Prep& p, const void* x, long long rows, int C, acc_t* sum, acc_t* sumsq,
+                            long long hi_off) {
+  const int nb = colstats_grid(rows, C / p.eg);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((colstats_kernel<T_, GRAD>), dim3(nb), dim3(kThreads), kFlushLdsBytes, p.st,
+                                       (const T_*)x, rows, C, sum, sumsq, hi_off));
+}
+
+extern "C" int kd6d_colstats(int dtype, const void* x, int64_t rows, int C, kd6d_acc* sum,
+                             kd6d_acc* sumsq, void* stream) {
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, 0, stream, &p), "kd6d_colstats: bad dtype %d", dtype);
+  KD6D_CHECK_ARG(colstats_channels_ok(C, p.eg), "kd6d_colstats: C=%d must be a multiple of %d and <= %d", C, p.eg,
+                 p.eg * kThreads);
   KD6D_CHECK_ARG(x && rows > 0, "kd6d_colstats: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int rpp = kThreads / (C / eg);
-  long long nb = (rows + (long long)rpp * 8 - 1) / ((long long)rpp * 8);
-  if (nb > kColstatsCap) nb = kColstatsCap;
-  if (nb < 1) nb = 1;
-  const size_t lds = kFlushLdsBytes;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(colstats_kernel<bf16_t>, dim3((int)nb), dim3(kThreads), lds, st,
-                                (const bf16_t*)x, (long long)rows, C, sum, sumsq, 0ll),
-             hipLaunchKernelGGL(colstats_kernel<float>, dim3((int)nb), dim3(kThreads), lds, st,
-                                (const float*)x, (long long)rows, C, sum, sumsq, 0ll));
+  launch_colstats<false>(dtype, p, x, rows, C, words(sum), words(sumsq), 0ll);
   KD6D_CHECK_LAUNCH("kd6d_colstats");
   return KD6D_OK;
 }
@@ -1532,8 +1532,8 @@ int kd6d_detail::gn_stats_levels(int src_f32, const void* y, const int* row0, co
                                  int G, unsigned mask, long long* stats, hipStream_t st) {
   KD6D_CHECK_ARG(y && stats && nseg >= 1 && nseg <= KD6D_MAX_SEG && batch >= 1 && G >= 1 && G <= 64 && C % G == 0,
                  "gn_stats_levels: bad arguments");
-  const int eg = src_f32 ? 4 : 8;
-  KD6D_CHECK_ARG(C % eg == 0 && (C / eg) <= 256 && 256 % (C / eg) == 0 && (C / G) * 2 >= eg, "gn_stats_levels: C=%d G=%d", C, G);
+  const int eg = granule_width(!src_f32);
+  KD6D_CHECK_ARG(channels_ok(C, eg) && (C / G) * 2 >= eg, "gn_stats_levels: C=%d G=%d", C, G);
   GnGeom gm;
   gm.nseg = nseg; gm.batch = batch; gm.C = C; gm.G = G;
   gm.chunk_rows = gn_chunk_rows();
@@ -1563,105 +1563,69 @@ int kd6d_detail::gn_stats_levels(int src_f32, const void* y, const int* row0, co
 // conv_igemm.hip (exact-fp32 weight gradient): the bias gradient as a separate column-sum pass
 int kd6d_detail::colsum_grad_planar(int dtype, const void* x, int64_t rows, int C, long long* acc, long long acc_hi,
                                     void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "colsum_grad_planar: bad dtype %d", dtype);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(C > 0 && C % eg == 0 && C / eg <= kThreads && x && acc && rows > 0, "colsum_grad_planar: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int rpp = kThreads / (C / eg);
-  long long nb = (rows + (long long)rpp * 8 - 1) / ((long long)rpp * 8);
-  if (nb > kColstatsCap) nb = kColstatsCap;
-  if (nb < 1) nb = 1;
-  const size_t lds = kFlushLdsBytes;
-  acc_t* none = nullptr;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((colstats_kernel<bf16_t, true>), dim3((int)nb), dim3(kThreads), lds, st,
-                                (const bf16_t*)x, (long long)rows, C, acc, none, acc_hi),
-             hipLaunchKernelGGL((colstats_kernel<float, true>), dim3((int)nb), dim3(kThreads), lds, st,
-                                (const float*)x, (long long)rows, C, acc, none, acc_hi));
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, 0, stream, &p), "colsum_grad_planar: bad dtype %d", dtype);
+  KD6D_CHECK_ARG(colstats_channels_ok(C, p.eg) && x && acc && rows > 0, "colsum_grad_planar: bad arguments");
+  launch_colstats<true>(dtype, p, x, rows, C, acc, nullptr, acc_hi);
   KD6D_CHECK_LAUNCH("colsum_grad_planar");
   return KD6D_OK;
 }
 
-#define DISPATCH_TTX(dtype, xf32, CALL)                                        \
-  do {                                                                         \
-    if ((dtype) == KD6D_F32) { typedef float T_; typedef float TX_; CALL; }     \
-    else if (xf32) { typedef bf16_t T_; typedef float TX_; CALL; }              \
-    else { typedef bf16_t T_; typedef bf16_t TX_; CALL; }                       \
-  } while (0)
-
-extern "C" int kd6d_bn_train_fwd(int dtype, int x_f32, const void* x, void* y, int64_t rows, int C,
-                                 const kd6d_acc* sum_acc, const kd6d_acc* sumsq_acc, const float* gamma,
-                                 const float* beta, float eps, float momentum, float* running_mean,
-                                 float* running_var, float* save_mean, float* save_invstd, int act,
-                                 void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_bn_train_fwd");
+// kd6d_bn_train_fwd and kd6d_bn_train_fwd_res (RES: the residual is added after the activation)
+template <bool RES>
+static int bn_train_fwd(const char* who, int dtype, int x_f32, const void* x, const void* residual, void* y, int64_t rows,
+                        int C, const kd6d_acc* sum, const kd6d_acc* sumsq, const float* gamma, const float* beta,
+                        float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
+                        float* save_invstd, int act, void* stream) {
+  Prep p;
+  int rc = check_channels(dtype, C, rows, stream, who, &p);
   if (rc) return rc;
-  const acc_t* sum = reinterpret_cast<const acc_t*>(sum_acc);
-  const acc_t* sumsq = reinterpret_cast<const acc_t*>(sumsq_acc);
-  KD6D_CHECK_ARG(x && y && sum && sumsq && gamma && beta && rows > 0, "kd6d_bn_train_fwd: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = rows * (C / eg);
+  KD6D_CHECK_ARG(x && y && sum && sumsq && gamma && beta && rows > 0, "%s: bad arguments", who);
+  KD6D_CHECK_ARG(!RES || residual, "%s: null residual", who);
   const float inv_rows = 1.f / (float)rows;
   const float unbias = rows > 1 ? (float)rows / (float)(rows - 1) : 1.f;
-  const int nb = grid_for((ngran + 3) / 4);
+  const int nb = grid_for((p.ngran + 3) / 4);
   DISPATCH_TTX(dtype, x_f32,
-               hipLaunchKernelGGL((bn_apply_fwd_kernel<T_, TX_>), dim3(nb), dim3(kThreads), 0, st,
-                                   (const TX_*)x, (T_*)y, ngran, C, inv_rows, sum, sumsq, gamma, beta, eps,
-                                   momentum, unbias, running_mean, running_var, save_mean, save_invstd, act));
-  KD6D_CHECK_LAUNCH("kd6d_bn_train_fwd");
+               hipLaunchKernelGGL((bn_apply_fwd_kernel<T_, TX_, RES>), dim3(nb), dim3(kThreads), 0, p.st,
+                                   (const TX_*)x, (T_*)y, p.ngran, C, inv_rows, words(sum), words(sumsq), gamma, beta, eps,
+                                   momentum, unbias, running_mean, running_var, save_mean, save_invstd, act,
+                                   (const T_*)residual));
+  KD6D_CHECK_LAUNCH(who);
   return KD6D_OK;
 }
 
+extern "C" int kd6d_bn_train_fwd(int dtype, int x_f32, const void* x, void* y, int64_t rows, int C,
+                                 const kd6d_acc* sum, const kd6d_acc* sumsq, const float* gamma,
+                                 const float* beta, float eps, float momentum, float* running_mean,
+                                 float* running_var, float* save_mean, float* save_invstd, int act,
+                                 void* stream) {
+  return bn_train_fwd<false>("kd6d_bn_train_fwd", dtype, x_f32, x, nullptr, y, rows, C, sum, sumsq, gamma, beta, eps,
+                             momentum, running_mean, running_var, save_mean, save_invstd, act, stream);
+}
+
 extern "C" int kd6d_bn_train_fwd_res(int dtype, int x_f32, const void* x, const void* residual, void* y, int64_t rows,
-                                     int C, const kd6d_acc* sum_acc, const kd6d_acc* sumsq_acc, const float* gamma,
+                                     int C, const kd6d_acc* sum, const kd6d_acc* sumsq, const float* gamma,
                                      const float* beta, float eps, float momentum, float* running_mean,
                                      float* running_var, float* save_mean, float* save_invstd, int act, void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_bn_train_fwd_res");
-  if (rc) return rc;
-  const acc_t* sum = reinterpret_cast<const acc_t*>(sum_acc);
-  const acc_t* sumsq = reinterpret_cast<const acc_t*>(sumsq_acc);
-  KD6D_CHECK_ARG(x && y && sum && sumsq && gamma && beta && rows > 0, "kd6d_bn_train_fwd_res: bad arguments");
-  KD6D_CHECK_ARG(residual, "kd6d_bn_train_fwd_res: null residual");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = rows * (C / eg);
-  const float inv_rows = 1.f / (float)rows;
-  const float unbias = rows > 1 ? (float)rows / (float)(rows - 1) : 1.f;
-  const int nb = grid_for((ngran + 3) / 4);
-  DISPATCH_TTX(dtype, x_f32,
-               hipLaunchKernelGGL((bn_apply_fwd_kernel<T_, TX_, true>), dim3(nb), dim3(kThreads), 0, st,
-                                   (const TX_*)x, (T_*)y, ngran, C, inv_rows, sum, sumsq, gamma, beta, eps,
-                                   momentum, unbias, running_mean, running_var, save_mean, save_invstd, act,
-                                   (const T_*)residual));
-  KD6D_CHECK_LAUNCH("kd6d_bn_train_fwd_res");
-  return KD6D_OK;
+  return bn_train_fwd<true>("kd6d_bn_train_fwd_res", dtype, x_f32, x, residual, y, rows, C, sum, sumsq, gamma, beta,
+                            eps, momentum, running_mean, running_var, save_mean, save_invstd, act, stream);
 }
 
 extern "C" int kd6d_bn_train_bwd_reduce(int dtype, int x_f32, const void* x, const void* dz, int64_t rows,
                                         int C, const float* mean, const float* invstd, const float* gamma,
-                                        const float* beta, int act, kd6d_acc* sum_dy_acc, kd6d_acc* sum_dy_xhat_acc,
+                                        const float* beta, int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat,
                                         int replicas, void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_bn_train_bwd_reduce");
+  Prep p;
+  int rc = check_channels(dtype, C, rows, stream, "kd6d_bn_train_bwd_reduce", &p);
   if (rc) return rc;
-  acc_t* sum_dy = reinterpret_cast<acc_t*>(sum_dy_acc);
-  acc_t* sum_dy_xhat = reinterpret_cast<acc_t*>(sum_dy_xhat_acc);
   KD6D_CHECK_ARG(replicas >= 1 && replicas <= 64, "kd6d_bn_train_bwd_reduce: replicas=%d outside [1,64]", replicas);
   KD6D_CHECK_ARG(x && dz && mean && invstd && gamma && beta && sum_dy && sum_dy_xhat && rows > 0,
                  "kd6d_bn_train_bwd_reduce: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = rows * (C / eg);
-  // every workgroup ends with one global atomic per channel and same-address atomics retire serially
-  // (~25 ns each): 2 workgroups per CU keep the loads in flight without a 1000-deep atomic queue
-  long long nb = (ngran + kThreads * 8 - 1) / (kThreads * 8);
-  if (nb > kBnBwdReduceCap) nb = kBnBwdReduceCap;
-  if (nb < 1) nb = 1;
-  const size_t lds = kFlushLdsBytes;
+  const int nb = bn_bwd_reduce_grid(p.ngran);
   DISPATCH_TTX(dtype, x_f32,
-               hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, TX_>), dim3((int)nb), dim3(kThreads), lds, st,
-                                   (const TX_*)x, (const T_*)dz, ngran, C, mean, invstd, gamma, beta, act, sum_dy,
-                                   sum_dy_xhat, replicas));
+               hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, TX_>), dim3(nb), dim3(kThreads), kFlushLdsBytes, p.st,
+                                   (const TX_*)x, (const T_*)dz, p.ngran, C, mean, invstd, gamma, beta, act, words(sum_dy),
+                                   words(sum_dy_xhat), replicas));
   KD6D_CHECK_LAUNCH("kd6d_bn_train_bwd_reduce");
   return KD6D_OK;
 }
@@ -1669,63 +1633,49 @@ extern "C" int kd6d_bn_train_bwd_reduce(int dtype, int x_f32, const void* x, con
 extern "C" int kd6d_bn_train_bwd_apply(int dtype, int x_f32, const void* x, const void* dz, void* dx,
                                        int64_t rows, int C, const float* mean, const float* invstd,
                                        const float* gamma, const float* beta, int act,
-                                       const kd6d_acc* sum_dy_acc, const kd6d_acc* sum_dy_xhat_acc, float* dgamma,
+                                       const kd6d_acc* sum_dy, const kd6d_acc* sum_dy_xhat, float* dgamma,
                                        float* dbeta, int replicas, void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_bn_train_bwd_apply");
+  Prep p;
+  int rc = check_channels(dtype, C, rows, stream, "kd6d_bn_train_bwd_apply", &p);
   if (rc) return rc;
-  const acc_t* sum_dy = reinterpret_cast<const acc_t*>(sum_dy_acc);
-  const acc_t* sum_dy_xhat = reinterpret_cast<const acc_t*>(sum_dy_xhat_acc);
   KD6D_CHECK_ARG(replicas >= 1 && replicas <= 64, "kd6d_bn_train_bwd_apply: replicas=%d outside [1,64]", replicas);
   KD6D_CHECK_ARG(x && dz && dx && mean && invstd && gamma && beta && sum_dy && sum_dy_xhat && rows > 0,
                  "kd6d_bn_train_bwd_apply: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = rows * (C / eg);
-  const int nb = grid_for((ngran + 3) / 4);
+  const int nb = grid_for((p.ngran + 3) / 4);
   const float inv_rows = 1.f / (float)rows;
   DISPATCH_TTX(dtype, x_f32,
                hipLaunchKernelGGL((bn_bwd_apply_kernel<T_, TX_>), dim3(nb), dim3(kThreads),
-                                   (size_t)2 * C * sizeof(float), st,
-                                   (const TX_*)x, (const T_*)dz, (T_*)dx, ngran, C, inv_rows, mean, invstd, gamma,
-                                   beta, act, sum_dy, sum_dy_xhat, dgamma, dbeta, replicas));   /* LDS: the totals as floats */
+                                   (size_t)bn_apply_lds_bytes(C), p.st,
+                                   (const TX_*)x, (const T_*)dz, (T_*)dx, p.ngran, C, inv_rows, mean, invstd, gamma,
+                                   beta, act, words(sum_dy), words(sum_dy_xhat), dgamma, dbeta, replicas));
   KD6D_CHECK_LAUNCH("kd6d_bn_train_bwd_apply");
   return KD6D_OK;
 }
 
 extern "C" int kd6d_bn_train_bwd(int dtype, int x_f32, const void* x, const void* dz, void* dx, int64_t rows, int C,
                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                 int act, kd6d_acc* sum_dy_acc, kd6d_acc* sum_dy_xhat_acc, unsigned int* counter, float* dgamma,
+                                 int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat, unsigned int* counter, float* dgamma,
                                  float* dbeta, int replicas, void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_bn_train_bwd");
+  Prep p;
+  int rc = check_channels(dtype, C, rows, stream, "kd6d_bn_train_bwd", &p);
   if (rc) return rc;
-  acc_t* sum_dy = reinterpret_cast<acc_t*>(sum_dy_acc);
-  acc_t* sum_dy_xhat = reinterpret_cast<acc_t*>(sum_dy_xhat_acc);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = rows * (C / eg);
-  int cap = 0;
-  DISPATCH_TTX(dtype, x_f32, cap = (bn_onepass_capacity<T_, TX_>(false)));
-  cap = cap * 3 / 4;                                      // the whole grid must be resident for the barrier
-  if (cap > kBnOnepassBlocks) cap = kBnOnepassBlocks;
-  if (!(counter && bn_onepass() && rows > 0 && cap > 0 && ngran <= (long long)cap * kThreads * kBnHold &&
-        ngran <= bn_onepass_max_granules())) {
-    rc = kd6d_bn_train_bwd_reduce(dtype, x_f32, x, dz, rows, C, mean, invstd, gamma, beta, act, sum_dy_acc, sum_dy_xhat_acc,
-                                  replicas, stream);
-    if (rc) return rc;
-    return kd6d_bn_train_bwd_apply(dtype, x_f32, x, dz, dx, rows, C, mean, invstd, gamma, beta, act, sum_dy_acc,
-                                   sum_dy_xhat_acc, dgamma, dbeta, replicas, stream);
-  }
   KD6D_CHECK_ARG(replicas >= 1 && replicas <= 64, "kd6d_bn_train_bwd: replicas=%d outside [1,64]", replicas);
   KD6D_CHECK_ARG(x && dz && dx && mean && invstd && gamma && beta && sum_dy && sum_dy_xhat,
                  "kd6d_bn_train_bwd: null pointer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  long long nb = (ngran + 2 * kThreads - 1) / (2 * kThreads);       // two granules per thread while the device has room
-  if (nb > cap) nb = cap;
-  const int per = (int)((ngran + nb * kThreads - 1) / (nb * kThreads));
+  KD6D_CHECK_ARG(rows > 0, "kd6d_bn_train_bwd: bad arguments");
+  const BnOnepassPlan plan = bn_plan(dtype, x_f32, false, p.ngran, counter != nullptr);
+  if (!plan.taken) {
+    rc = kd6d_bn_train_bwd_reduce(dtype, x_f32, x, dz, rows, C, mean, invstd, gamma, beta, act, sum_dy, sum_dy_xhat,
+                                  replicas, stream);
+    if (rc) return rc;
+    return kd6d_bn_train_bwd_apply(dtype, x_f32, x, dz, dx, rows, C, mean, invstd, gamma, beta, act, sum_dy,
+                                   sum_dy_xhat, dgamma, dbeta, replicas, stream);
+  }
   const float inv_rows = 1.f / (float)rows;
   DISPATCH_TTX(dtype, x_f32,
-               hipLaunchKernelGGL((bn_bwd_onepass_kernel<T_, TX_>), dim3((int)nb), dim3(kThreads),
-                                  (size_t)kFlushLdsBytes, st, (const TX_*)x, (const T_*)dz, (T_*)dx, ngran, per,
-                                  C, inv_rows, mean, invstd, gamma, beta, act, sum_dy, sum_dy_xhat, counter, dgamma,
+               hipLaunchKernelGGL((bn_bwd_onepass_kernel<T_, TX_>), dim3(plan.grid), dim3(kThreads), kFlushLdsBytes,
+                                  p.st, (const TX_*)x, (const T_*)dz, (T_*)dx, p.ngran, plan.per_thread, C, inv_rows,
+                                  mean, invstd, gamma, beta, act, words(sum_dy), words(sum_dy_xhat), counter, dgamma,
                                   dbeta, replicas, kd6d_ctx_timeouts_ptr()));
   KD6D_CHECK_LAUNCH("kd6d_bn_train_bwd");
   return KD6D_OK;
@@ -1740,36 +1690,31 @@ unsigned int* kd6d_detail::barrier_timeouts_device_ptr() {
   return ptr;
 }
 
-
-static int check_pool(int dtype, int B, int H, int W, int C, const char* who, long long* items) {
-  int rc = check_channels(dtype, C, who);
+// the pooled entry points: p->ngran counts 2x2 windows of granules, the kernels' work items
+static int check_pool(int dtype, int B, int H, int W, int C, void* stream, const char* who, Prep* p) {
+  int rc = check_channels(dtype, C, (long long)B * (H / 2) * (W / 2), stream, who, p);
   if (rc) return rc;
   KD6D_CHECK_ARG(B > 0 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "%s: B=%d H=%d W=%d (H, W must be even)", who, B, H, W);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  *items = (long long)B * (H / 2) * (W / 2) * (C / eg);
-  KD6D_CHECK_ARG(*items * 4 < (1ll << 31), "%s: %lld granules exceed the 32-bit item index", who, *items * 4);
+  KD6D_CHECK_ARG(p->ngran * 4 < (1ll << 31), "%s: %lld granules exceed the 32-bit item index", who, p->ngran * 4);
   return KD6D_OK;
 }
 
 extern "C" int kd6d_bn_pool_train_fwd(int dtype, int x_f32, const void* x, void* y, int B, int H, int W, int C,
-                                      const kd6d_acc* sum_acc, const kd6d_acc* sumsq_acc, const float* gamma,
+                                      const kd6d_acc* sum, const kd6d_acc* sumsq, const float* gamma,
                                       const float* beta, float eps, float momentum, float* running_mean,
                                       float* running_var, float* save_mean, float* save_invstd, int act,
                                       void* stream) {
-  const acc_t* sum = reinterpret_cast<const acc_t*>(sum_acc);
-  const acc_t* sumsq = reinterpret_cast<const acc_t*>(sumsq_acc);
-  long long items = 0;
-  int rc = check_pool(dtype, B, H, W, C, "kd6d_bn_pool_train_fwd", &items);
+  Prep p;
+  int rc = check_pool(dtype, B, H, W, C, stream, "kd6d_bn_pool_train_fwd", &p);
   if (rc) return rc;
   KD6D_CHECK_ARG(x && y && sum && sumsq && gamma && beta, "kd6d_bn_pool_train_fwd: null pointer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long long rows = (long long)B * H * W;
   const float inv_rows = 1.f / (float)rows;
   const float unbias = rows > 1 ? (float)rows / (float)(rows - 1) : 1.f;
-  const int nb = grid_for(items);
+  const int nb = grid_for(p.ngran);
   DISPATCH_TTX(dtype, x_f32,
-               hipLaunchKernelGGL((bn_pool_fwd_kernel<T_, TX_>), dim3(nb), dim3(kThreads), 0, st, (const TX_*)x,
-                                   (T_*)y, (int)items, H, W, C, inv_rows, sum, sumsq, gamma, beta, eps, momentum,
+               hipLaunchKernelGGL((bn_pool_fwd_kernel<T_, TX_>), dim3(nb), dim3(kThreads), 0, p.st, (const TX_*)x,
+                                   (T_*)y, (int)p.ngran, H, W, C, inv_rows, words(sum), words(sumsq), gamma, beta, eps, momentum,
                                    unbias, running_mean, running_var, save_mean, save_invstd, act));
   KD6D_CHECK_LAUNCH("kd6d_bn_pool_train_fwd");
   return KD6D_OK;
@@ -1777,48 +1722,32 @@ extern "C" int kd6d_bn_pool_train_fwd(int dtype, int x_f32, const void* x, void*
 
 extern "C" int kd6d_bn_pool_train_bwd(int dtype, int x_f32, const void* x, const void* dy, void* dx, int B, int H,
                                       int W, int C, const float* mean, const float* invstd, const float* gamma,
-                                      const float* beta, int act, kd6d_acc* sum_dy_acc, kd6d_acc* sum_dy_xhat_acc,
+                                      const float* beta, int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat,
                                       unsigned int* counter, float* dgamma, float* dbeta, int replicas,
                                       void* stream) {
-  acc_t* sum_dy = reinterpret_cast<acc_t*>(sum_dy_acc);
-  acc_t* sum_dy_xhat = reinterpret_cast<acc_t*>(sum_dy_xhat_acc);
-  long long items = 0;
-  int rc = check_pool(dtype, B, H, W, C, "kd6d_bn_pool_train_bwd", &items);
+  Prep p;
+  int rc = check_pool(dtype, B, H, W, C, stream, "kd6d_bn_pool_train_bwd", &p);
   if (rc) return rc;
   KD6D_CHECK_ARG(replicas >= 1 && replicas <= 64, "kd6d_bn_pool_train_bwd: replicas=%d outside [1,64]", replicas);
   KD6D_CHECK_ARG(x && dy && dx && mean && invstd && gamma && beta && sum_dy && sum_dy_xhat,
                  "kd6d_bn_pool_train_bwd: null pointer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int items = (int)p.ngran;
   const float inv_rows = 1.f / (float)((long long)B * H * W);
-  long long nbr = (items + kThreads * 2 - 1) / (kThreads * 2);      // 8 input granules per thread, as the unpooled pass
-  if (nbr > kBnBwdReduceCap) nbr = kBnBwdReduceCap;
-  if (nbr < 1) nbr = 1;
-  const int nba = grid_for(items);
-  const size_t lds = kFlushLdsBytes;
-  int cap = 0;
-  DISPATCH_TTX(dtype, x_f32, cap = (bn_onepass_capacity<T_, TX_>(true)));
-  cap = cap * 3 / 4;                                      // the whole grid must be resident for the barrier
-  if (cap > kBnOnepassBlocks) cap = kBnOnepassBlocks;
-  if (counter && bn_onepass() && cap > 0 && items <= (long long)cap * kThreads * kPoolHold &&
-      items * 4 <= bn_onepass_max_granules()) {
-    long long nb1 = (items + kThreads - 1) / kThreads;
-    if (nb1 > cap) nb1 = cap;
-    const int per = (int)((items + nb1 * kThreads - 1) / (nb1 * kThreads));
-    DISPATCH_TTX(dtype, x_f32,
-                 hipLaunchKernelGGL((bn_pool_bwd_onepass_kernel<T_, TX_>), dim3((int)nb1), dim3(kThreads), lds, st,
-                                    (const TX_*)x, (const T_*)dy, (T_*)dx, (int)items, per, H, W, C, inv_rows, mean,
-                                    invstd, gamma, beta, act, sum_dy, sum_dy_xhat, counter, dgamma, dbeta, replicas,
-                                    kd6d_ctx_timeouts_ptr()));
-    KD6D_CHECK_LAUNCH("kd6d_bn_pool_train_bwd");
-    return KD6D_OK;
-  }
+  const BnOnepassPlan plan = bn_plan(dtype, x_f32, true, items, counter != nullptr);
   DISPATCH_TTX(dtype, x_f32, {
-    hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<T_, TX_>), dim3((int)nbr), dim3(kThreads), lds, st,
-                       (const TX_*)x, (const T_*)dy, (int)items, H, W, C, mean, invstd, gamma, beta, act, sum_dy,
-                       sum_dy_xhat, replicas);
-    hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<T_, TX_>), dim3(nba), dim3(kThreads), lds, st, (const TX_*)x,
-                       (const T_*)dy, (T_*)dx, (int)items, H, W, C, inv_rows, mean, invstd, gamma, beta, act,
-                       sum_dy, sum_dy_xhat, dgamma, dbeta, replicas);
+    if (plan.taken) {
+      hipLaunchKernelGGL((bn_pool_bwd_onepass_kernel<T_, TX_>), dim3(plan.grid), dim3(kThreads), kFlushLdsBytes, p.st,
+                         (const TX_*)x, (const T_*)dy, (T_*)dx, items, plan.per_thread, H, W, C, inv_rows, mean,
+                         invstd, gamma, beta, act, words(sum_dy), words(sum_dy_xhat), counter, dgamma, dbeta, replicas,
+                         kd6d_ctx_timeouts_ptr());
+    } else {
+      hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<T_, TX_>), dim3(bn_pool_bwd_reduce_grid(items)), dim3(kThreads),
+                         kFlushLdsBytes, p.st, (const TX_*)x, (const T_*)dy, items, H, W, C, mean, invstd, gamma, beta,
+                         act, words(sum_dy), words(sum_dy_xhat), replicas);
+      hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<T_, TX_>), dim3(grid_for(items)), dim3(kThreads), kFlushLdsBytes,
+                         p.st, (const TX_*)x, (const T_*)dy, (T_*)dx, items, H, W, C, inv_rows, mean, invstd, gamma,
+                         beta, act, words(sum_dy), words(sum_dy_xhat), dgamma, dbeta, replicas);
+    }
   });
   KD6D_CHECK_LAUNCH("kd6d_bn_pool_train_bwd");
   return KD6D_OK;
@@ -1826,93 +1755,92 @@ extern "C" int kd6d_bn_pool_train_bwd(int dtype, int x_f32, const void* x, const
 
 extern "C" int kd6d_gn_relu_fwd(int dtype, int x_f32, const void* x, void* y, const int32_t* level_hw_host,
                                 int nseg, int batch, int C, int groups, const float* gamma,
-                                const float* beta, float eps, kd6d_acc* stats_acc, int flags, void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_gn_relu_fwd");
+                                const float* beta, float eps, kd6d_acc* stats, int flags, void* stream) {
+  Prep p;
+  int rc = check_channels(dtype, C, 0, stream, "kd6d_gn_relu_fwd", &p);
   if (rc) return rc;
-  acc_t* stats = reinterpret_cast<acc_t*>(stats_acc);
   GnGeom gm;
   KD6D_CHECK_ARG(level_hw_host && fill_gn(level_hw_host, nseg, batch, C, groups, &gm),
                  "kd6d_gn_relu_fwd: bad level table / groups");
   KD6D_CHECK_ARG(x && y && gamma && beta && stats, "kd6d_gn_relu_fwd: null pointer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = gn_rows(gm) * (C / eg);
-  const int nb = grid_for((ngran + 3) / 4);
-  KD6D_CHECK_ARG((C / groups) * 2 >= eg, "kd6d_gn_relu_fwd: C/groups=%d too small for %d-wide granules", C / groups, eg);
+  KD6D_CHECK_ARG((C / groups) * 2 >= p.eg, "kd6d_gn_relu_fwd: C/groups=%d too small for %d-wide granules", C / groups, p.eg);
+  const long long ngran = gn_rows(gm) * (C / p.eg);
+  gm.timeouts = kd6d_ctx_timeouts_ptr();
   const bool ready = flags & KD6D_GN_STATS_READY;
   if (!ready && !(flags & KD6D_GN_WS_ZEROED) &&
-      hipMemsetAsync(stats, 0, sizeof(kd6d_acc) * 2 * (size_t)nseg * batch * groups, st) != hipSuccess) {
+      hipMemsetAsync(stats, 0, sizeof(kd6d_acc) * 2 * (size_t)nseg * batch * groups, p.st) != hipSuccess) {
     kd6d_set_error("kd6d_gn_relu_fwd: memset failed");
     return KD6D_ERR_LAUNCH;
   }
   DISPATCH_TTX(dtype, x_f32, {
     if (!ready)
-      hipLaunchKernelGGL((gn_stats_kernel<T_, TX_>), dim3(gm.nblk), dim3(kThreads), 0, st, (const TX_*)x, gm, stats);
-    hipLaunchKernelGGL((gn_relu_fwd_kernel<T_, TX_>), dim3(nb), dim3(kThreads), 0, st, (const TX_*)x, (T_*)y, gm,
-                       ngran, eps, stats, gamma, beta);
+      hipLaunchKernelGGL((gn_stats_kernel<T_, TX_>), dim3(gm.nblk), dim3(kThreads), 0, p.st, (const TX_*)x, gm, words(stats));
+    hipLaunchKernelGGL((gn_relu_fwd_kernel<T_, TX_>), dim3(grid_for((ngran + 3) / 4)), dim3(kThreads), 0, p.st,
+                       (const TX_*)x, (T_*)y, gm, ngran, eps, words(stats), gamma, beta);
   });
   KD6D_CHECK_LAUNCH("kd6d_gn_relu_fwd");
   return KD6D_OK;
 }
 
+// ---- GN backward: what the single and the paired launcher share ----
+// option gn.onepass = 0: the two-launch GN backward (reduce, apply)
+static bool gn_onepass() { return kd6d_opt(KD6D_OPT_GN_ONEPASS) != 0; }
+// The kernels' red[] is launched with kFlushLdsBytes whatever C is (the residency of the barrier kernels was
+// established at that size), so wider tensors are refused.
+static bool gn_bwd_lds_fits(int C) { return gn_bwd_lds_bytes(C) <= kFlushLdsBytes; }
+// the launch geometry: the one-pass form's row chunks when it is on
+static bool gn_bwd_geometry(const Prep& p, const int32_t* level_hw, int nseg, int batch, int C, int groups, GnGeom* gm) {
+  return level_hw && fill_gn(level_hw, nseg, batch, C, groups, gm, gn_onepass() ? gn_onepass_chunk_rows(C, p.eg) : 0);
+}
+// the barrier counters of a workspace; clearing it (sums and counters are contiguous) unless the caller did
+static unsigned int* gn_counters(kd6d_acc* gsum_ws, const GnBwdWorkspace& ws) {
+  return reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(gsum_ws) + ws.counters_offset);
+}
+static int gn_clear_ws(kd6d_acc* gsum_ws, const GnBwdWorkspace& ws, int flags, hipStream_t st, const char* who) {
+  if ((flags & KD6D_GN_WS_ZEROED) || hipMemsetAsync(gsum_ws, 0, (size_t)ws.total_bytes, st) == hipSuccess) return KD6D_OK;
+  kd6d_set_error("%s: memset failed", who);
+  return KD6D_ERR_LAUNCH;
+}
+
 extern "C" int kd6d_gn_relu_bwd(int dtype, int x_f32, const void* x, const void* dz, void* dx,
                                 const int32_t* level_hw_host, int nseg, int batch, int C, int groups,
-                                const float* gamma, const float* beta, float eps, const kd6d_acc* stats_acc,
-                                kd6d_acc* gsum_ws_acc, int64_t* dgamma_acc, int64_t* dbeta_acc, int64_t acc_hi_stride,
+                                const float* gamma, const float* beta, float eps, const kd6d_acc* stats,
+                                kd6d_acc* gsum_ws, int64_t* dgamma, int64_t* dbeta, int64_t acc_hi_stride,
                                 int flags, void* stream) {
-  int rc = check_channels(dtype, C, "kd6d_gn_relu_bwd");
+  Prep p;
+  int rc = check_channels(dtype, C, 0, stream, "kd6d_gn_relu_bwd", &p);
   if (rc) return rc;
-  const acc_t* stats = reinterpret_cast<const acc_t*>(stats_acc);
-  acc_t* gsum_ws = reinterpret_cast<acc_t*>(gsum_ws_acc);
-  acc_t* dgamma = reinterpret_cast<acc_t*>(dgamma_acc);
-  acc_t* dbeta = reinterpret_cast<acc_t*>(dbeta_acc);
-  const long long acc_hi = (long long)acc_hi_stride;
+  KD6D_CHECK_ARG(gn_bwd_lds_fits(C), "kd6d_gn_relu_bwd: C=%d exceeds the limit of %d channels (32*C bytes of LDS, %d launched)",
+                 C, kGnBwdMaxC, kFlushLdsBytes);
   KD6D_CHECK_ARG((!dgamma && !dbeta) || acc_hi_stride != 0, "kd6d_gn_relu_bwd: acc_hi_stride = 0 with gradient accumulators");
   GnGeom gm;
-  KD6D_CHECK_ARG(level_hw_host && fill_gn(level_hw_host, nseg, batch, C, groups, &gm),
-                 "kd6d_gn_relu_bwd: bad level table / groups");
+  KD6D_CHECK_ARG(gn_bwd_geometry(p, level_hw_host, nseg, batch, C, groups, &gm), "kd6d_gn_relu_bwd: bad level table / groups");
   KD6D_CHECK_ARG(x && dz && dx && gamma && beta && stats && gsum_ws, "kd6d_gn_relu_bwd: null pointer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  const long long ngran = gn_rows(gm) * (C / eg);
-  const int nb = grid_for((ngran + 3) / 4);
-  const size_t lds = kFlushLdsBytes;
-  KD6D_CHECK_ARG((C / groups) * 2 >= eg, "kd6d_gn_relu_bwd: C/groups=%d too small for %d-wide granules", C / groups, eg);
-  if (!(flags & KD6D_GN_WS_ZEROED) &&
-      hipMemsetAsync(gsum_ws, 0, sizeof(kd6d_acc) * 2 * (size_t)nseg * batch * groups, st) != hipSuccess) {
-    kd6d_set_error("kd6d_gn_relu_bwd: memset failed");
-    return KD6D_ERR_LAUNCH;
+  KD6D_CHECK_ARG((C / groups) * 2 >= p.eg, "kd6d_gn_relu_bwd: C/groups=%d too small for %d-wide granules", C / groups, p.eg);
+  const bool onepass = gn_onepass();
+  if (onepass) {
+    const int cap = resident(dtype, x_f32, kGnOnepass);
+    const GnOnepassPlan plan = gn_onepass_plan(C, p.eg, level_hw_host, nseg, cap, 2);
+    KD6D_CHECK_ARG(plan.fits, "kd6d_gn_relu_bwd: a level of %d row chunks does not fit the %d resident workgroups "
+                   "(set option gn.onepass = 0)", plan.siblings, cap);
   }
-  if (gn_onepass()) {
-    // row chunks small enough for the registers of one workgroup; the barrier counters sit behind the sums
-    const int cgs = C / eg;
-    int chunk = gn_chunk_rows();
-    if (chunk * cgs > kGnHold * kThreads) chunk = kGnHold * kThreads / cgs;
-    GnGeom g1;
-    KD6D_CHECK_ARG(chunk >= 1 && fill_gn(level_hw_host, nseg, batch, C, groups, &g1, chunk), "kd6d_gn_relu_bwd: geometry");
-    int gcap = 0, gmax = 1;
-    DISPATCH_TTX(dtype, x_f32, gcap = (gn_onepass_capacity<T_, TX_>()));
-    for (int s = 0; s < nseg; ++s) gmax = g1.cps[s] > gmax ? g1.cps[s] : gmax;
-    KD6D_CHECK_ARG(gcap >= 2 * gmax, "kd6d_gn_relu_bwd: a level of %d row chunks does not fit the %d resident workgroups "
-                   "(set option gn.onepass = 0)", gmax, gcap);
-    unsigned int* counters = reinterpret_cast<unsigned int*>(gsum_ws + 4 * (size_t)nseg * batch * groups);
-    if (!(flags & KD6D_GN_WS_ZEROED) &&
-        hipMemsetAsync(counters, 0, sizeof(unsigned int) * (size_t)nseg * batch, st) != hipSuccess) {
-      kd6d_set_error("kd6d_gn_relu_bwd: memset failed");
-      return KD6D_ERR_LAUNCH;
-    }
-    DISPATCH_TTX(dtype, x_f32,
-                 hipLaunchKernelGGL((gn_relu_bwd_onepass_kernel<T_, TX_>), dim3(g1.nblk), dim3(kThreads), lds, st,
-                                    (const TX_*)x, (const T_*)dz, (T_*)dx, g1, eps, stats, gamma, beta, gsum_ws,
-                                    counters, dgamma, dbeta, acc_hi));
-    KD6D_CHECK_LAUNCH("kd6d_gn_relu_bwd");
-    return KD6D_OK;
-  }
+  const GnBwdWorkspace ws = gn_bwd_workspace(nseg, batch, groups);
+  rc = gn_clear_ws(gsum_ws, ws, flags, p.st, "kd6d_gn_relu_bwd");
+  if (rc) return rc;
+  gm.timeouts = kd6d_ctx_timeouts_ptr();
+  const long long ngran = gn_rows(gm) * (C / p.eg), acc_hi = acc_hi_stride;
   DISPATCH_TTX(dtype, x_f32, {
-    hipLaunchKernelGGL((gn_relu_bwd_reduce_kernel<T_, TX_>), dim3(gm.nblk), dim3(kThreads), lds, st,
-                       (const TX_*)x, (const T_*)dz, gm, eps, stats, gamma, beta, gsum_ws, dgamma, dbeta, acc_hi);
-    hipLaunchKernelGGL((gn_relu_bwd_apply_kernel<T_, TX_>), dim3(nb), dim3(kThreads), 0, st, (const TX_*)x,
-                       (const T_*)dz, (T_*)dx, gm, ngran, eps, stats, gsum_ws, gamma, beta);
+    if (onepass) {
+      hipLaunchKernelGGL((gn_relu_bwd_onepass_kernel<T_, TX_>), dim3(gm.nblk), dim3(kThreads), kFlushLdsBytes, p.st,
+                         (const TX_*)x, (const T_*)dz, (T_*)dx, gm, eps, words(stats), gamma, beta, words(gsum_ws),
+                         gn_counters(gsum_ws, ws), words(dgamma), words(dbeta), acc_hi);
+    } else {
+      hipLaunchKernelGGL((gn_relu_bwd_reduce_kernel<T_, TX_>), dim3(gm.nblk), dim3(kThreads), kFlushLdsBytes, p.st,
+                         (const TX_*)x, (const T_*)dz, gm, eps, words(stats), gamma, beta, words(gsum_ws), words(dgamma),
+                         words(dbeta), acc_hi);
+      hipLaunchKernelGGL((gn_relu_bwd_apply_kernel<T_, TX_>), dim3(grid_for((ngran + 3) / 4)), dim3(kThreads), 0, p.st,
+                         (const TX_*)x, (const T_*)dz, (T_*)dx, gm, ngran, eps, words(stats), words(gsum_ws), gamma, beta);
+    }
   });
   KD6D_CHECK_LAUNCH("kd6d_gn_relu_bwd");
   return KD6D_OK;
@@ -1922,24 +1850,22 @@ extern "C" int kd6d_gn_relu_bwd_pair(int dtype, int x_f32, const kd6d_gn_item* a
                                      const int32_t* level_hw_host, int nseg, int batch, int C, int groups, float eps,
                                      int64_t acc_hi_stride, int flags, void* stream) {
   KD6D_CHECK_ARG(a && b, "kd6d_gn_relu_bwd_pair: null item");
-  // the one-launch form exists for the in-kernel-barrier backward only; everything else goes out one by one
-  int chunk = 0;
-  GnGeom g1;
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  bool pair = gn_onepass() && check_channels(dtype, C, "kd6d_gn_relu_bwd_pair") == KD6D_OK && level_hw_host;
-  if (pair) {
-    const int cgs = C / eg;
-    chunk = gn_chunk_rows();
-    if (chunk * cgs > kGnHold * kThreads) chunk = kGnHold * kThreads / cgs;
-    pair = chunk >= 1 && (C / groups) * 2 >= eg && fill_gn(level_hw_host, nseg, batch, C, groups, &g1, chunk);
-  }
-  if (pair) {
-    int gcap = 0, gmax = 1;
-    DISPATCH_TTX(dtype, x_f32, gcap = (gn_onepass_capacity<T_, TX_>()));
-    for (int s = 0; s < nseg; ++s) gmax = g1.cps[s] > gmax ? g1.cps[s] : gmax;
-    pair = gcap >= 4 * gmax;                 // two launches' worth of siblings resident at once
-  }
   const kd6d_gn_item* it[2] = {a, b};
+  // the one-launch form exists for the in-kernel-barrier backward only; everything else goes out one by one, and
+  // kd6d_gn_relu_bwd reports what is wrong with the arguments
+  Prep p;
+  GnGeom g1;
+  bool pair = gn_onepass() && check_channels(dtype, C, 0, stream, "kd6d_gn_relu_bwd_pair", &p) == KD6D_OK &&
+              gn_bwd_lds_fits(C) && gn_bwd_geometry(p, level_hw_host, nseg, batch, C, groups, &g1) &&
+              (C / groups) * 2 >= p.eg;
+  for (int i = 0; pair && i < 2; ++i) {
+    KD6D_CHECK_ARG(it[i]->x && it[i]->dz && it[i]->dx && it[i]->gamma && it[i]->beta && it[i]->stats && it[i]->gsum_ws,
+                   "kd6d_gn_relu_bwd_pair: null pointer in item %d", i);
+    KD6D_CHECK_ARG((!it[i]->dgamma && !it[i]->dbeta) || acc_hi_stride != 0,
+                   "kd6d_gn_relu_bwd_pair: acc_hi_stride = 0 with gradient accumulators");
+  }
+  // two launches' worth of siblings resident at once
+  pair = pair && gn_onepass_plan(C, p.eg, level_hw_host, nseg, resident(dtype, x_f32, kGnOnepass), 4).fits;
   if (!pair) {
     for (int i = 0; i < 2; ++i) {
       const int rc = kd6d_gn_relu_bwd(dtype, x_f32, it[i]->x, it[i]->dz, it[i]->dx, level_hw_host, nseg, batch, C, groups,
@@ -1949,134 +1875,87 @@ extern "C" int kd6d_gn_relu_bwd_pair(int dtype, int x_f32, const kd6d_gn_item* a
     }
     return KD6D_OK;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const GnBwdWorkspace ws = gn_bwd_workspace(nseg, batch, groups);
   GnBwdSet sets[2];
   for (int i = 0; i < 2; ++i) {
-    KD6D_CHECK_ARG(it[i]->x && it[i]->dz && it[i]->dx && it[i]->gamma && it[i]->beta && it[i]->stats && it[i]->gsum_ws,
-                   "kd6d_gn_relu_bwd_pair: null pointer in item %d", i);
-    KD6D_CHECK_ARG((!it[i]->dgamma && !it[i]->dbeta) || acc_hi_stride != 0,
-                   "kd6d_gn_relu_bwd_pair: acc_hi_stride = 0 with gradient accumulators");
-    unsigned int* counters = reinterpret_cast<unsigned int*>(it[i]->gsum_ws + 2 * (size_t)nseg * batch * groups);   // kd6d_acc units
-    if (!(flags & KD6D_GN_WS_ZEROED) &&
-        hipMemsetAsync(it[i]->gsum_ws, 0, sizeof(kd6d_acc) * 2 * (size_t)nseg * batch * groups + sizeof(unsigned int) * (size_t)nseg * batch,
-                       st) != hipSuccess) {
-      kd6d_set_error("kd6d_gn_relu_bwd_pair: memset failed");
-      return KD6D_ERR_LAUNCH;
-    }
-    sets[i] = GnBwdSet{it[i]->x, it[i]->dz, it[i]->dx, reinterpret_cast<const acc_t*>(it[i]->stats), it[i]->gamma,
-                       it[i]->beta, reinterpret_cast<acc_t*>(it[i]->gsum_ws), counters,
-                       reinterpret_cast<acc_t*>(it[i]->dgamma), reinterpret_cast<acc_t*>(it[i]->dbeta)};
+    const int rc = gn_clear_ws(it[i]->gsum_ws, ws, flags, p.st, "kd6d_gn_relu_bwd_pair");
+    if (rc) return rc;
+    sets[i] = GnBwdSet{it[i]->x, it[i]->dz, it[i]->dx, words(it[i]->stats), it[i]->gamma, it[i]->beta,
+                       words(it[i]->gsum_ws), gn_counters(it[i]->gsum_ws, ws), words(it[i]->dgamma), words(it[i]->dbeta)};
   }
-  const size_t lds = kFlushLdsBytes;
+  g1.timeouts = kd6d_ctx_timeouts_ptr();
   DISPATCH_TTX(dtype, x_f32,
-               hipLaunchKernelGGL((gn_relu_bwd_onepass_pair_kernel<T_, TX_>), dim3(2 * g1.nblk), dim3(kThreads), lds, st,
-                                  sets[0], sets[1], g1, eps, (long long)acc_hi_stride));
+               hipLaunchKernelGGL((gn_relu_bwd_onepass_pair_kernel<T_, TX_>), dim3(2 * g1.nblk), dim3(kThreads),
+                                  kFlushLdsBytes, p.st, sets[0], sets[1], g1, eps, (long long)acc_hi_stride));
   KD6D_CHECK_LAUNCH("kd6d_gn_relu_bwd_pair");
   return KD6D_OK;
 }
 
-extern "C" int kd6d_maxpool2_fwd(int dtype, const void* x, void* y, int B, int H, int W, int C,
-                                 void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_maxpool2_fwd: bad dtype");
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(x && y && B > 0 && H >= 2 && W >= 2 && C % eg == 0, "kd6d_maxpool2_fwd: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long total = (long long)B * (H / 2) * (W / 2) * (C / eg);
-  const int nb = grid_for(total);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(maxpool2_fwd_kernel<bf16_t>, dim3(nb), dim3(kThreads), 0, st,
-                                (const bf16_t*)x, (bf16_t*)y, B, H, W, C),
-             hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, dim3(nb), dim3(kThreads), 0, st,
-                                (const float*)x, (float*)y, B, H, W, C));
+extern "C" int kd6d_maxpool2_fwd(int dtype, const void* x, void* y, int B, int H, int W, int C, void* stream) {
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, (long long)B * (H / 2) * (W / 2) * C, stream, &p), "kd6d_maxpool2_fwd: bad dtype");
+  KD6D_CHECK_ARG(x && y && B > 0 && H >= 2 && W >= 2 && C % p.eg == 0, "kd6d_maxpool2_fwd: bad arguments");
+  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_fwd_kernel<T_>, dim3(grid_for(p.ngran)), dim3(kThreads), 0, p.st,
+                                       (const T_*)x, (T_*)y, B, H, W, C));
   KD6D_CHECK_LAUNCH("kd6d_maxpool2_fwd");
   return KD6D_OK;
 }
 
 extern "C" int kd6d_maxpool2_bwd(int dtype, const void* x, const void* dy, void* dx, int B, int H,
                                  int W, int C, int accumulate, void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_maxpool2_bwd: bad dtype");
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(x && dy && dx && B > 0 && H >= 2 && W >= 2 && C % eg == 0 && H % 2 == 0 && W % 2 == 0,
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, (long long)B * (H / 2) * (W / 2) * C, stream, &p), "kd6d_maxpool2_bwd: bad dtype");
+  KD6D_CHECK_ARG(x && dy && dx && B > 0 && H >= 2 && W >= 2 && C % p.eg == 0 && H % 2 == 0 && W % 2 == 0,
                  "kd6d_maxpool2_bwd: bad arguments (H, W must be even)");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long total = (long long)B * (H / 2) * (W / 2) * (C / eg);
-  const int nb = grid_for(total);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16_t>, dim3(nb), dim3(kThreads), 0, st,
-                                (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C, accumulate),
-             hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, dim3(nb), dim3(kThreads), 0, st,
-                                (const float*)x, (const float*)dy, (float*)dx, B, H, W, C, accumulate));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_bwd_kernel<T_>, dim3(grid_for(p.ngran)), dim3(kThreads), 0, p.st,
+                                       (const T_*)x, (const T_*)dy, (T_*)dx, B, H, W, C, accumulate));
   KD6D_CHECK_LAUNCH("kd6d_maxpool2_bwd");
   return KD6D_OK;
 }
 
 extern "C" int kd6d_upsample2_add(int dtype, const void* fine, const void* coarse, void* out, int B,
                                   int H, int W, int C, void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_upsample2_add: bad dtype");
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(fine && coarse && out && B > 0 && H % 2 == 0 && W % 2 == 0 && C % eg == 0,
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, (long long)B * H * W * C, stream, &p), "kd6d_upsample2_add: bad dtype");
+  KD6D_CHECK_ARG(fine && coarse && out && B > 0 && H % 2 == 0 && W % 2 == 0 && C % p.eg == 0,
                  "kd6d_upsample2_add: bad arguments (H, W must be even)");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long total = (long long)B * H * W * (C / eg);
-  const int nb = grid_for(total);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(upsample2_add_kernel<bf16_t>, dim3(nb), dim3(kThreads), 0, st,
-                                (const bf16_t*)fine, (const bf16_t*)coarse, (bf16_t*)out, B, H, W, C),
-             hipLaunchKernelGGL(upsample2_add_kernel<float>, dim3(nb), dim3(kThreads), 0, st,
-                                (const float*)fine, (const float*)coarse, (float*)out, B, H, W, C));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(upsample2_add_kernel<T_>, dim3(grid_for(p.ngran)), dim3(kThreads), 0, p.st,
+                                       (const T_*)fine, (const T_*)coarse, (T_*)out, B, H, W, C));
   KD6D_CHECK_LAUNCH("kd6d_upsample2_add");
   return KD6D_OK;
 }
 
 extern "C" int kd6d_sumpool2(int dtype, const void* dfine, void* dcoarse, int B, int H, int W, int C,
                              int accumulate, void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_sumpool2: bad dtype");
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(dfine && dcoarse && B > 0 && H % 2 == 0 && W % 2 == 0 && C % eg == 0,
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, (long long)B * (H / 2) * (W / 2) * C, stream, &p), "kd6d_sumpool2: bad dtype");
+  KD6D_CHECK_ARG(dfine && dcoarse && B > 0 && H % 2 == 0 && W % 2 == 0 && C % p.eg == 0,
                  "kd6d_sumpool2: bad arguments (H, W must be even)");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long total = (long long)B * (H / 2) * (W / 2) * (C / eg);
-  const int nb = grid_for(total);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(sumpool2_kernel<bf16_t>, dim3(nb), dim3(kThreads), 0, st,
-                                (const bf16_t*)dfine, (bf16_t*)dcoarse, B, H, W, C, accumulate),
-             hipLaunchKernelGGL(sumpool2_kernel<float>, dim3(nb), dim3(kThreads), 0, st,
-                                (const float*)dfine, (float*)dcoarse, B, H, W, C, accumulate));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(sumpool2_kernel<T_>, dim3(grid_for(p.ngran)), dim3(kThreads), 0, p.st,
+                                       (const T_*)dfine, (T_*)dcoarse, B, H, W, C, accumulate));
   KD6D_CHECK_LAUNCH("kd6d_sumpool2");
   return KD6D_OK;
 }
 
-extern "C" int kd6d_eltwise(int dtype, int mode, const void* x, const void* dy, void* y,
-                            int64_t n_elems, void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_eltwise: bad dtype");
-  const int eg = dtype == KD6D_BF16 ? 8 : 4;
-  KD6D_CHECK_ARG(x && y && n_elems > 0 && n_elems % eg == 0 && mode >= 0 && mode <= 2 &&
-                     (mode == 0 || dy),
+extern "C" int kd6d_eltwise(int dtype, int mode, const void* x, const void* dy, void* y, int64_t n_elems, void* stream) {
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, n_elems, stream, &p), "kd6d_eltwise: bad dtype");
+  KD6D_CHECK_ARG(x && y && n_elems > 0 && n_elems % p.eg == 0 && mode >= 0 && mode <= 2 && (mode == 0 || dy),
                  "kd6d_eltwise: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long ngran = n_elems / eg;
-  const int nb = grid_for(ngran);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(eltwise_kernel<bf16_t>, dim3(nb), dim3(kThreads), 0, st,
-                                (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)y, ngran, mode),
-             hipLaunchKernelGGL(eltwise_kernel<float>, dim3(nb), dim3(kThreads), 0, st,
-                                (const float*)x, (const float*)dy, (float*)y, ngran, mode));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(eltwise_kernel<T_>, dim3(grid_for(p.ngran)), dim3(kThreads), 0, p.st,
+                                       (const T_*)x, (const T_*)dy, (T_*)y, p.ngran, mode));
   KD6D_CHECK_LAUNCH("kd6d_eltwise");
   return KD6D_OK;
 }
 
 extern "C" int kd6d_image_to_nhwc(int dtype, const float* img_nchw, void* out, int B, int Cimg, int H,
                                   int W, int Cpad, void* stream) {
-  KD6D_CHECK_ARG(dtype == KD6D_BF16 || dtype == KD6D_F32, "kd6d_image_to_nhwc: bad dtype");
+  Prep p;
+  KD6D_CHECK_ARG(prep(dtype, 0, stream, &p), "kd6d_image_to_nhwc: bad dtype");
   KD6D_CHECK_ARG(img_nchw && out && B > 0 && Cimg > 0 && Cpad >= Cimg && H > 0 && W > 0,
                  "kd6d_image_to_nhwc: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nb = grid_for((long long)B * H * W);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(image_to_nhwc_kernel<bf16_t>, dim3(nb), dim3(kThreads), 0, st, img_nchw,
-                                (bf16_t*)out, B, Cimg, H, W, Cpad),
-             hipLaunchKernelGGL(image_to_nhwc_kernel<float>, dim3(nb), dim3(kThreads), 0, st, img_nchw,
-                                (float*)out, B, Cimg, H, W, Cpad));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(image_to_nhwc_kernel<T_>, dim3(grid_for((long long)B * H * W)), dim3(kThreads), 0,
+                                       p.st, img_nchw, (T_*)out, B, Cimg, H, W, Cpad));
   KD6D_CHECK_LAUNCH("kd6d_image_to_nhwc");
   return KD6D_OK;
 }

@@ -503,7 +503,8 @@ def gn_relu_fwd(x, y, level_hw, batch, groups, gamma, beta, eps, stats, flags=0)
 
 
 def gn_bwd_workspace_floats(n_levels, batch, groups):
-    """fp32 slots of kd6d_gn_relu_bwd's workspace: the group-sum accumulators plus one barrier counter per (level, image)."""
+    """fp32 slots of kd6d_gn_relu_bwd's workspace: the group-sum accumulators plus one barrier counter per (level, image)
+    (the launchers' copy of the layout: csrc/norm_plan.h, gn_bwd_workspace; tests/test_norm_plan_host.py ties the two)."""
     return 2 * n_levels * batch * groups * ACC_FLOATS + n_levels * batch
 
 

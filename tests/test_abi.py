@@ -47,6 +47,13 @@ def test_argument_checks_fail_loudly_without_gpu():
     except _lib.Kd6dError as e:
         assert "null pointer" in str(e)
     assert lib.kd6d_sinkhorn_max_points() >= 64
+    # GroupNorm backward: 32*C bytes of LDS accumulators in a 16-KB launch -- C = 1024 passes the channel rule, not this one
+    p = ctypes.c_void_p(64)         # never dereferenced: the calls below fail their argument checks on the host
+    hw = (ctypes.c_int32 * 2)(64, 16)
+    rc = lib.kd6d_gn_relu_bwd(_lib.KD6D_BF16, 1, p, p, p, hw, 2, 2, 1024, 32, p, p, 1e-5, p, p, p, p, 2048, 0, None)
+    assert rc == -1 and b"C=1024" in lib.kd6d_last_error() and b"limit of 512 channels" in lib.kd6d_last_error()
+    rc = lib.kd6d_bn_train_bwd(_lib.KD6D_BF16, 1, p, p, p, 100, 16, p, p, p, p, 1, p, p, p, p, p, 99, None)
+    assert rc == -1 and b"kd6d_bn_train_bwd: replicas=99" in lib.kd6d_last_error()
 
 
 def test_kernel_selection_options_table():

@@ -671,12 +671,13 @@ def test_colstats_any_channel_count(gpu_device, dtype, C, rows):
 
 
 @pytest.mark.parametrize("dtype,xf32", MIXED)
-@pytest.mark.parametrize("C", [128, 256])
+@pytest.mark.parametrize("C", [128, 256, 512])
 @pytest.mark.parametrize("levels,onepass", [([(6, 6), (3, 3), (2, 2), (1, 1)], "1"), ([(6, 6), (3, 3), (2, 2), (1, 1)], "0"),
                                             ([(32, 32), (16, 12), (5, 5)], "1"), ([(32, 32), (16, 12), (5, 5)], "0")])
 def test_groupnorm_relu_fwd_bwd(gpu_device, dtype, xf32, C, levels, onepass):
     """onepass "1": the backward is one kernel whose workgroups of a (level, image) meet at an in-kernel barrier
-    (32x32 levels span 8..32 workgroups); "0": the reduce + apply pair."""
+    (32x32 levels span 8..32 workgroups); "0": the reduce + apply pair.  C = 512 is the widest tensor the backward
+    accepts: its per-channel LDS accumulators fill the launch's 16 KB exactly, one-pass row chunks of 32 / 16 rows."""
     ops = _ops()
     dev = gpu_device
     _option("gn.onepass", int(onepass))
@@ -717,15 +718,17 @@ def test_groupnorm_relu_fwd_bwd(gpu_device, dtype, xf32, C, levels, onepass):
 
 
 @pytest.mark.parametrize("onepass", [1, 0])
-@pytest.mark.parametrize("levels", [[(32, 32), (16, 16), (8, 8), (4, 4), (2, 2)], [(6, 6), (3, 3), (1, 1)]])
-def test_groupnorm_bwd_pair_equals_two_launches(gpu_device, levels, onepass):
+@pytest.mark.parametrize("levels,C", [pytest.param([(32, 32), (16, 16), (8, 8), (4, 4), (2, 2)], 128, id="levels0"),
+                                      pytest.param([(6, 6), (3, 3), (1, 1)], 128, id="levels1"),
+                                      pytest.param([(6, 6), (3, 3), (1, 1)], 512, id="levels1-C512")])
+def test_groupnorm_bwd_pair_equals_two_launches(gpu_device, levels, C, onepass):
     """kd6d_gn_relu_bwd_pair: the two tower layers' GroupNorm backwards in one launch give what two launches give
     (dx to one bf16 ulp on a few elements -- same code, group sums differ by atomic order; dgamma / dbeta to
     atomic-order noise); with gn.onepass = 0 the entry falls back to two launch pairs."""
     ops = _ops()
     dev = gpu_device
     _option("gn.onepass", onepass)
-    B, G, C = 4, 32, 128
+    B, G = 4, 32
     hw = [h * w for (h, w) in levels]
     rows = B * sum(hw)
     g = torch.Generator().manual_seed(11)
