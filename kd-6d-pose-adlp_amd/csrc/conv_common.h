@@ -6,15 +6,19 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "conv_plan.h"
 #include "kd6d_barrier.h"
 #include "kd6d_common.h"
 #include "kd6d_det.h"
 
 namespace kd6d_detail {
 
-
-constexpr int kMaxSeg = KD6D_MAX_SEG;
-enum { MODE_FWD = 0, MODE_DGRAD = 1 };
+using kd6d_conv::kMaxSeg;
+enum { MODE_FWD = kd6d_conv::kFwd, MODE_DGRAD = kd6d_conv::kDgrad };
+static_assert(kMaxSeg == KD6D_MAX_SEG && kd6d_conv::kNormMaxCtiles == KD6D_NORM_MAX_CTILES &&
+                  kd6d_conv::kBf16 == KD6D_BF16 && kd6d_conv::kF32 == KD6D_F32 &&
+                  kd6d_conv::kNormGroup == KD6D_NORM_GROUP && kd6d_conv::kNormBatch == KD6D_NORM_BATCH,
+              "conv_plan.h restates constants of kd6d.h");
 
 struct SegDev {
   int src_h, src_w;    // gather-source grid
@@ -799,43 +803,38 @@ static inline int check_geom(const kd6d_conv_geom* g, int dtype, const char* who
   return KD6D_OK;
 }
 
-// Workgroup order.  After the XCD remap an XCD runs a CONTIGUOUS range of ~1/8 of the tile ids, so the
-// fastest-varying tile index decides which operand that XCD's 4 MiB L2 can keep: channel tiles fastest
-// -> the XCD touches few pixel tiles but ALL weights; pixel tiles fastest -> few weight tiles but many
-// pixels.  Pick the order with the smaller per-XCD footprint (small-M / wide-N layers: weights).
-static inline void set_tile_order(ConvParams& q, int ptiles, int BP, int BC) {
-  q.n_ptiles = ptiles;
-  const double tiles = (double)ptiles * q.n_ctiles;
-  const double per_xcd = tiles / 8.0;
-  const double w_tile = (double)BC * q.K * 2.0, x_tile = (double)BP * q.C * 2.0 * (q.ks > 1 ? 1.5 : 1.0);
-  // channel tiles fastest: an XCD spans per_xcd / n_ctiles pixel tiles (>= 1) and min(per_xcd, n_ctiles) weight tiles
-  auto foot = [&](double n_fast, double t_fast, double t_slow) {
-    const double fast = per_xcd < n_fast ? per_xcd : n_fast;
-    const double slow = per_xcd / n_fast < 1.0 ? 1.0 : per_xcd / n_fast;
-    return fast * t_fast + slow * t_slow;
-  };
-  const double c_fast = foot(q.n_ctiles, w_tile, x_tile);
-  const double p_fast = foot(ptiles, x_tile, w_tile);
-  q.p_fastest = p_fast < c_fast ? 1 : 0;
-}
-
 static inline int cached_cu_count() {       // one device per process
   static const int n = []() { const int c = kd6d_device_cu_count(); return c > 0 ? c : 256; }();
   return n;
 }
 
-// Dry run of the forward dispatch (kd6d_conv2d_fwd_norm_fusable): while g_launch_plan is set, the launch functions
-// record what they would launch instead of launching it.
-struct LaunchPlan {
-  int grid = 0, threads = 0;
-  size_t lds = 0;
-  bool fused_epilogue = false;     // the kernel ends in conv_epilogue_full
-};
-extern thread_local LaunchPlan* g_launch_plan;
-static inline bool plan_only(int grid, int threads, size_t lds, bool fused_epilogue) {
-  if (!g_launch_plan) return false;
-  g_launch_plan->grid = grid; g_launch_plan->threads = threads; g_launch_plan->lds = lds;
-  g_launch_plan->fused_epilogue = fused_epilogue;
+// ---- the dispatch plan (conv_plan.h) from the library's side ----
+// the GEMM the rules read: p as fwd_params / kd6d_conv2d_dgrad fill it, the levels in forward sense from g
+static inline kd6d_conv::Shape plan_shape(const kd6d_conv_geom* g, int M, int N, int C, int K) {
+  kd6d_conv::Shape s = {M, N, C, K, g->ksize, g->stride, g->pad, g->batch, g->nseg, {}};
+  for (int i = 0; i < g->nseg; ++i) s.seg[i] = {g->seg[i].in_h, g->seg[i].in_w, g->seg[i].in_row0, g->seg[i].out_row0};
+  return s;
+}
+static inline kd6d_conv::Options plan_options() {
+  kd6d_conv::Options o;
+  o.halo = (int)kd6d_opt(KD6D_OPT_CONV_HALO); o.halo_pairing = (int)kd6d_opt(KD6D_OPT_CONV_HALO_PAIRING);
+  o.halo_wide = (int)kd6d_opt(KD6D_OPT_CONV_HALO_WIDE); o.smallc = (int)kd6d_opt(KD6D_OPT_CONV_SMALLC);
+  o.smallc_wmax = (int)kd6d_opt(KD6D_OPT_CONV_SMALLC_WMAX); o.splitk = (int)kd6d_opt(KD6D_OPT_CONV_SPLITK);
+  o.tile = (int)kd6d_opt(KD6D_OPT_CONV_TILE); o.wgrad_small = (int)kd6d_opt(KD6D_OPT_WGRAD_SMALL);
+  return o;
+}
+// the launch's copy of the parameters with the planned fields in
+static inline ConvParams planned_params(const ConvParams& p, const kd6d_conv::FwdPlan& pl) {
+  ConvParams q = p;
+  q.n_ctiles = pl.n_ctiles; q.n_ptiles = pl.n_ptiles; q.p_fastest = pl.p_fastest; q.nk_split = pl.nk_split;
+  return q;
+}
+
+// launch Kern with its LDS opt-in (kd6d_raise_lds_limit) in place
+template <auto Kern, typename... Args>
+static inline bool launch_kernel(dim3 grid, int threads, long long lds, hipStream_t st, const Args&... args) {
+  kd6d_raise_lds_limit<Kern>((size_t)lds);
+  hipLaunchKernelGGL(Kern, grid, dim3(threads), (size_t)lds, st, args...);
   return true;
 }
 
@@ -844,8 +843,8 @@ int stats_followup(const ConvParams& p, bool dst_f32, hipStream_t st);
 // norm_ops.hip: {sum, sum of squares} per (level, image, group) of the levels in `mask` of a packed NHWC tensor
 int gn_stats_levels(int src_f32, const void* y, const int* row0, const int* hw, int nseg, int batch, int C, int G,
                     unsigned mask, long long* stats, hipStream_t st);
-// conv_halo.hip: the 3x3 / stride 1 halo-patch kernel takes the layer (returns false: not its shape / too few tiles)
-bool dispatch_halo_fwd(const ConvParams& p, const kd6d_conv_geom* g, hipStream_t st);
-bool dispatch_halo_dgrad(const ConvParams& p, const kd6d_conv_geom* g, hipStream_t st);
+// conv_halo.hip: launch a kHalo plan (or record it, inside a pair bracket); is the calling thread's context inside one?
+bool launch_halo(const kd6d_conv::FwdPlan& pl, const ConvParams& p, hipStream_t st);
+bool pair_bracket_active();
 
 }  // namespace kd6d_detail

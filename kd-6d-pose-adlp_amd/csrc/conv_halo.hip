@@ -254,7 +254,8 @@ __global__ __launch_bounds__(WP* WC * 64, PDB ? 1 : WP * WC / 2) void conv3x3_ha
 // recorded launches of the same kernel variant and geometry go out as one conv3x3_halo_pair_kernel launch.
 struct HaloRecord {
   ConvParams q;
-  int halo, total_rows, tiles;
+  int halo, total_rows, tiles, threads;
+  long long lds;
   hipStream_t st;
   void (*single)(const HaloRecord&);
   void (*pair)(const HaloRecord&, const HaloRecord&);
@@ -275,158 +276,45 @@ PairState& pair_state() {
 }
 #define g_pair (pair_state())
 
-template <int BP, int BC, int WP, int WC, int MODE, int HMAX, bool PDB>
-size_t halo_lds() {
-  constexpr int NW = WP * WC;
-  constexpr int PSLOT = (BP + 2 * HMAX + 7) / 8 + 1;
-  constexpr int PL = (PSLOT + NW - 1) / NW;
-  return (PDB ? (size_t)2 * PL * NW : (size_t)PSLOT) * 1024 + (size_t)3 * BC * 128;
-}
-
-template <int BP, int BC, int WP, int WC, int MODE, int HMAX = 65, bool PDB = true, bool NORM = false>
+template <int BP, int BC, int WP, int WC, int MODE, int HMAX, bool PDB, bool NORM>
 void halo_issue_single(const HaloRecord& r) {
-  const size_t lds = halo_lds<BP, BC, WP, WC, MODE, HMAX, PDB>();
-  auto kern = conv3x3_halo_kernel<BP, BC, WP, WC, MODE, HMAX, PDB, NORM>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(r.tiles), dim3(WP * WC * 64), lds, r.st, r.q, r.halo, r.total_rows);
+  launch_kernel<conv3x3_halo_kernel<BP, BC, WP, WC, MODE, HMAX, PDB, NORM>>(dim3(r.tiles), r.threads, r.lds, r.st, r.q, r.halo,
+                                                                            r.total_rows);
 }
 
-template <int BP, int BC, int WP, int WC, int MODE, int HMAX = 65, bool PDB = true, bool NORM = false>
+template <int BP, int BC, int WP, int WC, int MODE, int HMAX, bool PDB, bool NORM>
 void halo_issue_pair(const HaloRecord& a, const HaloRecord& b) {
-  const size_t lds = halo_lds<BP, BC, WP, WC, MODE, HMAX, PDB>();
-  auto kern = conv3x3_halo_pair_kernel<BP, BC, WP, WC, MODE, HMAX, PDB, NORM>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.tiles + b.tiles), dim3(WP * WC * 64), lds, a.st, a.q, b.q, a.halo, a.total_rows,
-                     a.tiles);
-}
-
-template <int BP, int BC, int WP, int WC, int MODE, int HMAX = 65, bool PDB = true, bool NORM = false>
-void launch_halo(const ConvParams& p, int halo, int total_rows, hipStream_t st) {
-  HaloRecord r;
-  r.q = p;
-  r.q.n_ctiles = (p.N + BC - 1) / BC;
-  const int ptiles = (p.M + BP - 1) / BP;
-  set_tile_order(r.q, ptiles, BP, BC);
-  r.halo = halo; r.total_rows = total_rows; r.tiles = ptiles * r.q.n_ctiles; r.st = st;
-  r.single = &halo_issue_single<BP, BC, WP, WC, MODE, HMAX, PDB, NORM>;
-  r.pair = &halo_issue_pair<BP, BC, WP, WC, MODE, HMAX, PDB, NORM>;
-  if (plan_only(r.tiles, WP * WC * 64, halo_lds<BP, BC, WP, WC, MODE, HMAX, PDB>(), NORM)) return;
-  if (g_pair.active && g_pair.count < 2) { g_pair.rec[g_pair.count++] = r; return; }
-  r.single(r);
-}
-
-// 3x3/s1/p1 layers with C % 64 == 0 on maps at most 80 wide, both sides packed identically.
-template <int MODE>
-bool dispatch_halo(const ConvParams& p, const kd6d_conv_geom* g, hipStream_t st) {
-  const int force = (int)kd6d_opt(KD6D_OPT_CONV_HALO);
-  if (force == 0) return false;
-  if (p.ks != 3 || p.stride != 1 || p.pad != 1 || (p.C & 63) || (p.N & 3)) return false;
-  if (p.N < 64 && p.N > 32) return false;
-  if (!p.norm_dst && p.stats_replicas > 1) return false;      // replica rows of the batch statistics: register-staged kernel
-  int wmax = 0, rows = 0;
-  for (int s = 0; s < g->nseg; ++s) {
-    const kd6d_seg& q = g->seg[s];
-    if (q.in_row0 != q.out_row0 || q.in_row0 != rows) return false;
-    if (q.in_w > wmax) wmax = q.in_w;
-    rows += g->batch * q.in_h * q.in_w;
-  }
-  if (wmax > (kd6d_opt(KD6D_OPT_CONV_HALO_WIDE) != 0 ? 80 : 64)) return false;      // (80: the 60 x 80 level of 480 x 640 full frames)
-  const int halo = wmax + 1;
-  // measured on the step's layers (tools/bench_conv.py), all variants with 8 waves (2 per SIMD: with 4 waves
-  // the same 128x128 tile is 25-40 % slower, one wave per SIMD cannot hide the LDS-DMA / fragment latency):
-  //   256x128 once it yields >= 150 workgroups (teacher head, stage 2);
-  //   128x128 from >= 160 workgroups (teacher stage 3, FPN 32x32 level, student head towers fwd + dgrad);
-  //   128x64  from >= 64 workgroups (teacher stage 4, student FPN 32x32 level) -- ahead of split-K;
-  //   192x128 / 64x64 / 128x32: the tile-count corner cases below;
-  // below that the layer goes to split-K / the generic kernels.
-  // inside a kd6d_conv2d_pair_begin/_end bracket the launch shares the device with its twin: count tiles twice
-  const int pf = g_pair.active ? 2 : 1;
-  const int pt128 = pf * ((p.M + 127) / 128);
-  int pick = 0;
-  const int ct128 = (p.N + 127) / 128;
-  const int ncu = cached_cu_count();
-  const int ct64 = (p.N + 63) / 64;
-  // few result channels (cls logits, dgrad into the narrow student stages): 128 x 32, or 64 x 64 on small maps
-  if (p.N <= 32) pick = pt128 <= ncu / 2 ? 9 : 5;
-  // 128 x 64 tiles would occupy at most half of the CUs: 64 x 64 (FPN 16x16 level, stage 5, student FPN)
-  else if (pt128 * ct64 <= ncu / 2 && pf * ((p.M + 63) / 64) * ct64 >= 64) pick = 9;
-  // 192 x 128 where it turns 256-pixel tiles that leave a third of the CUs idle into one full round (teacher head
-  // towers: 172 tiles of 256 pixels on 256 CUs -> 228 tiles of 192)
-  else if (pf * ((p.M + 255) / 256) * ct128 >= 150 && pf * ((p.M + 255) / 256) * ct128 <= (3 * ncu) / 4 &&
-           pf * ((p.M + 191) / 192) * ct128 <= ncu) pick = 6;
-  else if (pf * ((p.M + 255) / 256) * ((p.N + 127) / 128) >= 150) pick = 1;
-  else if (pt128 * ((p.N + 127) / 128) >= 160) pick = 3;
-  else if (pt128 * ((p.N + 63) / 64) >= 64) pick = 4;
-  // maps up to 32 wide (halo <= 33): the single-patch-buffer twin of the picked tile, 38-74 KB of LDS instead of
-  // 104-144, so that two workgroups -- of this launch or of the other stream's -- share a CU.  Alone on the device a
-  // twin is as fast as its original or up to 40 % slower (chunk-boundary stalls, no partner to cover them); inside
-  // the step the pairs give +4 % (4889-4918 -> 5097 images/s, interleaved runs; profiles/r02_halo_pairing.md)
-  if (kd6d_opt(KD6D_OPT_CONV_HALO_PAIRING) != 0 && halo <= 33) {
-    // (96 x 128 tiles for the 342-tile tower shape -- 456 tiles on 512 slots instead of 86 CUs carrying two tiles of 128 x
-    //  128 and 170 one -- were built and measured in round 3: 5064-5099 against 5184-5192 images/s, interleaved; removed)
-    // (256 x 128, one workgroup per CU, is what the counts above pick from ~40 000 rows on -- the teacher's towers over
-    //  the 32 images of a grouped pass: 2.25 us per image against 1.75 for the twins, 1.91 for 192 x 128; tools/bench_conv.py
-    //  --batch 32 --opt conv.halo=N)
-    if (pick == 3 || pick == 6 || pick == 1) pick = 12;
-    else if (pick == 4) pick = 13;
-    else if (pick == 9) pick = 14;
-    else if (pick == 5) pick = 15;
-  }
-  if (force > 0 && (force < 10 || halo <= 33)) pick = force;      // 11..15: the twins, maps <= 32 wide only
-  if (pick == 0) return false;
-  if (p.norm_dst) {
-    // a fused normalisation behind the convolution (kd6d_conv2d_fwd_norm): compiled into the 128 x 128 forward tiles only
-    if constexpr (MODE == MODE_FWD) {
-      if (halo > 65) launch_halo<128, 128, 4, 2, MODE, 81, true, true>(p, halo, rows, st);
-      else if (halo > 33 || kd6d_opt(KD6D_OPT_CONV_HALO_PAIRING) == 0) launch_halo<128, 128, 4, 2, MODE, 65, true, true>(p, halo, rows, st);
-      else launch_halo<128, 128, 4, 2, MODE, 33, false, true>(p, halo, rows, st);
-      return true;
-    }
-    return false;
-  }
-  if (pick == 11) { launch_halo<128, 128, 2, 2, MODE, 33, false>(p, halo, rows, st); return true; }
-  if (pick == 12) { launch_halo<128, 128, 4, 2, MODE, 33, false>(p, halo, rows, st); return true; }
-  if (pick == 13) { launch_halo<128, 64, 4, 2, MODE, 33, false>(p, halo, rows, st); return true; }
-  if (pick == 14) { launch_halo<64, 64, 4, 2, MODE, 33, false>(p, halo, rows, st); return true; }
-  if (pick == 15) { launch_halo<128, 32, 4, 1, MODE, 33, false>(p, halo, rows, st); return true; }
-  if (halo > 65) {
-    // maps 65 ... 80 wide: the same tiles with the patch sized for a halo of 81 rows (the 256 x 128 tile then takes
-    // exactly the CU's 160 KB)
-    if (pick == 1) launch_halo<256, 128, 4, 2, MODE, 81>(p, halo, rows, st);
-    else if (pick == 3 || pick == 6) launch_halo<128, 128, 4, 2, MODE, 81>(p, halo, rows, st);
-    else if (pick == 4) launch_halo<128, 64, 4, 2, MODE, 81>(p, halo, rows, st);
-    else if (pick == 5) launch_halo<128, 32, 4, 1, MODE, 81>(p, halo, rows, st);
-    else if (pick == 9) launch_halo<64, 64, 4, 2, MODE, 81>(p, halo, rows, st);
-    else launch_halo<128, 128, 4, 2, MODE, 81>(p, halo, rows, st);
-    return true;
-  }
-  if (pick == 1) launch_halo<256, 128, 4, 2, MODE>(p, halo, rows, st);
-  else if (pick == 3) launch_halo<128, 128, 4, 2, MODE>(p, halo, rows, st);      // 8 waves on the 128x128 tile
-  else if (pick == 4) launch_halo<128, 64, 4, 2, MODE>(p, halo, rows, st);
-  else if (pick == 5) launch_halo<128, 32, 4, 1, MODE>(p, halo, rows, st);
-  else if (pick == 6) launch_halo<192, 128, 4, 2, MODE>(p, halo, rows, st);
-  else if (pick == 9) launch_halo<64, 64, 4, 2, MODE>(p, halo, rows, st);
-  else launch_halo<128, 128, 2, 2, MODE>(p, halo, rows, st);
-  return true;
+  launch_kernel<conv3x3_halo_pair_kernel<BP, BC, WP, WC, MODE, HMAX, PDB, NORM>>(dim3(a.tiles + b.tiles), a.threads, a.lds, a.st,
+                                                                                 a.q, b.q, a.halo, a.total_rows, a.tiles);
 }
 
 }  // namespace
 
-bool kd6d_detail::dispatch_halo_fwd(const ConvParams& p, const kd6d_conv_geom* g, hipStream_t st) {
-  return dispatch_halo<MODE_FWD>(p, g, st);
-}
-bool kd6d_detail::dispatch_halo_dgrad(const ConvParams& p, const kd6d_conv_geom* g, hipStream_t st) {
-  return dispatch_halo<MODE_DGRAD>(p, g, st);
+bool kd6d_detail::pair_bracket_active() { return g_pair.active; }
+
+// the planned variant's instantiation (KD6D_CONV_HALO_TILES, conv_plan.h): issued, or recorded inside a pair bracket
+bool kd6d_detail::launch_halo(const kd6d_conv::FwdPlan& pl, const ConvParams& p, hipStream_t st) {
+  HaloRecord r;
+  r.q = planned_params(p, pl);
+  r.halo = pl.halo; r.total_rows = pl.total_rows; r.tiles = pl.grid_x; r.threads = pl.threads; r.lds = pl.lds_bytes;
+  r.st = st; r.single = nullptr; r.pair = nullptr;
+#define KD6D_HALO_CASE(m_, n_, bp, bc, wp, wc, hmax, pdb)                                                          \
+  if (pl.mode == m_ && pl.NORM == n_ && pl.BP == bp && pl.BC == bc && pl.WP == wp && pl.WC == wc && pl.HMAX == hmax && \
+      pl.PDB == pdb) {                                                                                             \
+    r.single = &halo_issue_single<bp, bc, wp, wc, m_, hmax, pdb, n_>;                                              \
+    r.pair = &halo_issue_pair<bp, bc, wp, wc, m_, hmax, pdb, n_>;                                                  \
+  }
+#define KD6D_HALO_BOTH(...) KD6D_HALO_CASE(MODE_FWD, false, __VA_ARGS__) KD6D_HALO_CASE(MODE_DGRAD, false, __VA_ARGS__)
+#define KD6D_HALO_NORM(...) KD6D_HALO_CASE(MODE_FWD, true, __VA_ARGS__)
+  KD6D_CONV_HALO_TILES(KD6D_HALO_BOTH)
+  KD6D_CONV_HALO_NORM_TILES(KD6D_HALO_NORM)
+#undef KD6D_HALO_NORM
+#undef KD6D_HALO_BOTH
+#undef KD6D_HALO_CASE
+  if (!r.single) return false;
+  if (g_pair.active && g_pair.count < 2) { g_pair.rec[g_pair.count++] = r; return true; }
+  r.single(r);
+  return true;
 }
 
 #undef g_pair

@@ -665,7 +665,6 @@ struct WgradParams {
   const void* dy;
   float* dw;          // slab: partial image of split s at dw + s * Cout * J (plain stores)
   long long slab_floats;
-  int* plan_splits;   // host: non-null = dry run, the launch function reports its number of partial images here
   long long* dbias;   // optional: += column sums of dY (bias gradient), planar accumulators (hi word at + acc_hi),
   long long acc_hi;   //           added by the j-tile-0 workgroups
   int cu_budget;  // CUs this launch should aim to fill (callers that run several weight gradients side by side)
@@ -1279,386 +1278,128 @@ __global__ __launch_bounds__(256) void pack_dgrad_kernel(const T* __restrict__ w
 }
 
 
-template <typename T, int BP, int BC, int WP, int WC, int MODE, bool XF = false, bool NORM = false>
-void launch_igemm_impl(const ConvParams& p, hipStream_t st) {
-  ConvParams q = p;
-  q.n_ctiles = (p.N + BC - 1) / BC;
-  const int ptiles = (p.M + BP - 1) / BP;
-  set_tile_order(q, ptiles, BP, BC);
-  const size_t lds = (size_t)(BP + BC) * 128 * 2 + (XF ? (size_t)2 * p.C * sizeof(float) : 0);
-  if (plan_only(ptiles * q.n_ctiles, 256, lds, NORM)) return;
-  auto kern = conv_igemm_kernel<T, BP, BC, WP, WC, MODE, XF, NORM>;
-  static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_lds = lds;
+// ---------------------------------------------------------------------------
+// host side: plan (conv_plan.h), then launch what the plan says.  A launch function finds the planned variant in its
+// family's list and launches that instantiation with the planned grid, block, LDS and arguments; false = the list has no
+// such variant (an error for the caller, never another kernel).
+// ---------------------------------------------------------------------------
+using kd6d_conv::FwdPlan;
+using kd6d_conv::WgradPlan;
+
+template <typename T, int MODE, bool XF>
+bool launch_igemm(const FwdPlan& pl, const ConvParams& q, hipStream_t st) {
+  const dim3 grid(pl.grid_x, pl.grid_y);
+#define KD6D_CASE(bp, bc, wp, wc)                                                                                    \
+  if (pl.BP == bp && pl.BC == bc) {                                                                                  \
+    if constexpr (MODE == MODE_FWD && !XF) {                                                                         \
+      if (pl.NORM)                                                                                                   \
+        return launch_kernel<conv_igemm_kernel<T, bp, bc, wp, wc, MODE, false, true>>(grid, pl.threads, pl.lds_bytes, st, q); \
+    }                                                                                                                \
+    return launch_kernel<conv_igemm_kernel<T, bp, bc, wp, wc, MODE, XF, false>>(grid, pl.threads, pl.lds_bytes, st, q);  \
   }
-  hipLaunchKernelGGL(kern, dim3(ptiles * q.n_ctiles), dim3(256), lds, st, q);
-}
-
-// the fused-normalisation epilogue exists in the forward, non-XF variants only (kd6d_conv2d_fwd_norm)
-template <typename T, int BP, int BC, int WP, int WC, int MODE, bool XF = false>
-void launch_igemm(const ConvParams& p, hipStream_t st) {
-  if constexpr (MODE == MODE_FWD && !XF) {
-    // ... and so do the replica rows of the fused batch statistics (kd6d_conv2d_fwd_block)
-    if (p.norm_dst || p.stats_replicas > 1) { launch_igemm_impl<T, BP, BC, WP, WC, MODE, false, true>(p, st); return; }
-  }
-  launch_igemm_impl<T, BP, BC, WP, WC, MODE, XF, false>(p, st);
-}
-
-template <int BP, int BC, int WP, int WC, int MODE, int NSTAGE>
-void launch_glds(const ConvParams& p, hipStream_t st) {
-  ConvParams q = p;
-  q.n_ctiles = (p.N + BC - 1) / BC;
-  const int ptiles = (p.M + BP - 1) / BP;
-  set_tile_order(q, ptiles, BP, BC);
-  const size_t lds = (size_t)(BP + BC) * 128 * NSTAGE;
-  if (plan_only(ptiles * q.n_ctiles, 256, lds, false)) return;
-  auto kern = conv_igemm_glds_kernel<BP, BC, WP, WC, MODE, NSTAGE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(ptiles * q.n_ctiles), dim3(256), lds, st, q);
-}
-
-
-
-template <int CG, int NB, int MODE>
-void launch_smallc(const ConvParams& p, int halo, int total_rows, hipStream_t st) {
-  constexpr int BP = 256, BC = 16 * NB;
-  constexpr int NKC = (9 * 8 * CG + 31) / 32, WG = NKC * 4 + 1;
-  ConvParams q = p;
-  q.n_ctiles = (p.N + BC - 1) / BC;
-  const int ptiles = (p.M + BP - 1) / BP;
-  q.n_ptiles = ptiles;
-  // patch rows [m0 - halo, m0 + BP + halo) + the zero row, padded to whole 1-KB LDS-DMA bursts
-  const int patch_bytes = ((BP + 2 * halo + 1) * 16 * CG + 1023) / 1024 * 1024;
-  const size_t wbytes = (size_t)(BC * WG + 63) / 64 * 1024;
-  size_t lds = (size_t)patch_bytes + wbytes + 256 * sizeof(int);
-  const size_t epi = (size_t)2 * BC * sizeof(float) + 4096;      // statistics scratch of the epilogue
-  if (lds < epi) lds = epi;
-  auto kern = conv3x3_smallc_kernel<CG, NB, MODE>;
-  static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_lds = lds;
-  }
-  hipLaunchKernelGGL(kern, dim3(ptiles * q.n_ctiles), dim3(256), lds, st, q, halo, total_rows, patch_bytes, (int)wbytes);
-}
-
-// 3x3/s1/p1 layers with 8, 16 or 32 gather-source channels on maps up to 256 wide, both sides packed identically.
-template <int MODE>
-bool dispatch_smallc(const ConvParams& p, const kd6d_conv_geom* g, hipStream_t st) {
-  const int force = (int)kd6d_opt(KD6D_OPT_CONV_SMALLC);
-  if (force == 0) return false;
-  if (p.ks != 3 || p.stride != 1 || p.pad != 1 || (p.C != 8 && p.C != 16 && p.C != 32) || (p.N & 3)) return false;
-  if (p.stats && p.stats_groups > 0) return false;      // the group-statistics table wants the big staging buffers
-  if (p.norm_dst || p.stats_replicas > 1) return false;   // no fused-normalisation epilogue / replica rows in this kernel
-  // one burst per workgroup, no pipeline: pays once >= 2 workgroups per CU overlap each other (measured: the
-  // 64x64-pixel layers and below are faster on the pipelined kernels)
-  if (force < 0 && p.M < (1 << 17)) return false;
-  int wmax = 0, rows = 0;
-  for (int s = 0; s < g->nseg; ++s) {
-    const kd6d_seg& q = g->seg[s];
-    if (q.in_row0 != q.out_row0 || q.in_row0 != rows) return false;
-    if (q.in_w > wmax) wmax = q.in_w;
-    rows += g->batch * q.in_h * q.in_w;
-  }
-  // the patch is 256 pixels + a halo of (width + 1) rows on either side: up to 256-wide maps always (the size the kernel
-  // was tuned on), wider ones (the 640- and 320-wide levels of full frames) while it stays within 32 KB, i.e. 8 or 16
-  // channels -- read amplification (256 + 2 halo) / 256 grows to 6x at 640, all of it L2 hits, against 9 taps on the
-  // generic kernels: 480 x 640 x 8 -> 32 forward 298 -> 165 us, 8 -> 8 forward / dgrad 266 / 289 -> 78 / 79,
-  // 240 x 320 x 8 -> 16 71 / 90 -> 24 / 33; with 32 channels (57 KB, one or two workgroups per CU) 129 -> 216, excluded
-  if (wmax > 256 && (wmax > (int)kd6d_opt(KD6D_OPT_CONV_SMALLC_WMAX) || (256 + 2 * (wmax + 1) + 1) * 2 * p.C > 32768)) return false;
-  const int halo = wmax + 1;
-  const int nb = p.N <= 16 ? 1 : (p.N <= 32 ? 2 : (p.N <= 64 ? 4 : 8));
-#define KD6D_SMALLC_CASE(CG_, NB_) \
-  if (p.C == 8 * CG_ && nb == NB_) { launch_smallc<CG_, NB_, MODE>(p, halo, rows, st); return true; }
-  KD6D_SMALLC_CASE(1, 1) KD6D_SMALLC_CASE(1, 2) KD6D_SMALLC_CASE(1, 4) KD6D_SMALLC_CASE(1, 8)
-  KD6D_SMALLC_CASE(2, 1) KD6D_SMALLC_CASE(2, 2) KD6D_SMALLC_CASE(2, 4) KD6D_SMALLC_CASE(2, 8)
-  KD6D_SMALLC_CASE(4, 1) KD6D_SMALLC_CASE(4, 2) KD6D_SMALLC_CASE(4, 4) KD6D_SMALLC_CASE(4, 8)
-#undef KD6D_SMALLC_CASE
+  KD6D_CONV_IGEMM_TILES(KD6D_CASE)
+#undef KD6D_CASE
   return false;
 }
 
-template <int BP, int BC, int WP, int WC, int MODE, int NSTAGE>
-void launch_splitk(const ConvParams& p, int nsplit, hipStream_t st) {
-  ConvParams q = p;
-  q.n_ctiles = (p.N + BC - 1) / BC;
-  const int ptiles = (p.M + BP - 1) / BP;
-  set_tile_order(q, ptiles, BP, BC);
-  const int nk_all = (p.K + 63) / 64;
-  q.nk_split = (nk_all + nsplit - 1) / nsplit;
-  nsplit = (nk_all + q.nk_split - 1) / q.nk_split;
-  const size_t lds = (size_t)(BP + BC) * 128 * NSTAGE;
-  auto kern = conv_igemm_glds_kernel<BP, BC, WP, WC, MODE, NSTAGE, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(ptiles * q.n_ctiles, nsplit), dim3(256), lds, st, q);
-  const long long total = (long long)p.M * (p.N >> 2);
-  int nb = (int)((total + 255) / 256);
-  if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(splitk_finalize_kernel, dim3(nb), dim3(256), 0, st, q, nsplit);
-}
-
-// Split-K for the layers whose output yields too few tiles to fill 256 CUs while K is long (teacher
-// stages 4/5, FPN top: M <= 4096, K = 2304..9216): partial tiles go to fp32 slabs in the caller's
-// workspace (plain 16-B stores, no atomics), a small second launch sums them and applies the epilogue.
 template <int MODE>
-bool dispatch_splitk(const ConvParams& p, float* ws, size_t ws_bytes, hipStream_t st) {
-  const int force = (int)kd6d_opt(KD6D_OPT_CONV_SPLITK);
-  if (force == 0 || !ws || p.stats || (p.N & 3) || p.N <= 32) return false;
-  const int nk = (p.K + 63) / 64;
-  auto nblocks = [&](int bp, int bc) { return ((p.M + bp - 1) / bp) * ((p.N + bc - 1) / bc); };
-  int tile = 0, ns = 0;
-  if (force > 0) { tile = force / 100; ns = force % 100; }
-  else if (nk >= 16 && nblocks(64, 64) <= 320) {
-    tile = 2;
-    ns = 768 / nblocks(64, 64);
-    if (ns > nk / 6) ns = nk / 6;
-    if (ns > 16) ns = 16;
-  }
-  if (tile == 0 || ns < 2) return false;
-  if ((size_t)ns * p.M * p.N * sizeof(float) > ws_bytes) return false;
-  ConvParams q = p;
-  q.slab = ws;
-  if (tile == 1) launch_splitk<128, 64, 2, 2, MODE, 3>(q, ns, st);
-  else launch_splitk<64, 64, 2, 2, MODE, 3>(q, ns, st);
-  return true;
-}
-
-// bf16, N > 32: LDS-DMA kernel.  Tile by how many workgroups the layer yields (256 CUs).
-template <int MODE>
-bool dispatch_glds(const ConvParams& p, hipStream_t st) {
-  const int force = (int)kd6d_opt(KD6D_OPT_CONV_TILE);
-  if (force == 0 || p.N <= 32) return false;
-  // launches with a fused normalisation (kd6d_conv2d_fwd_norm) or replica rows of the batch statistics take the
-  // register-staged kernel: this one is not compiled with that epilogue (and its 64-KB rings would not leave a
-  // grid-barrier launch room to be resident at once)
-  if (p.norm_dst || p.stats_replicas > 1) return false;
-  const int N = p.N, M = p.M;
-  auto nblocks = [&](int bp, int bc) { return ((M + bp - 1) / bp) * ((N + bc - 1) / bc); };
-  // measured (tools/bench_conv.py): with enough workgroups the register-staged kernel is as fast or faster
-  // (several workgroups per CU hide the load round trip); the layers with <= ~1 workgroup per CU and a long
-  // K (teacher stages 4/5, FPN top) are bound by that round trip and gain from a deep LDS-DMA ring
-  int pick = 0;
-  if (nblocks(128, 64) < 384) pick = 3;
-  else if (nblocks(128, 64) <= 640 && p.K >= 1024) pick = 2;       // stride-2 stage-3 entry: 28 -> 25 us
-  // k-steps that straddle taps (source channels not a multiple of 64) pay a tap decode per step here; on the
-  // large maps (dgrad of the student's cls / pose heads) the register-staged kernel is 15-25 % faster
-  if (pick == 3 && (p.C & 63) && M > 16384) pick = 0;
-  if (force > 0) pick = force;
-  if (pick == 0) return false;
-  if (pick == 1) launch_glds<128, 128, 2, 2, MODE, 3>(p, st);
-  else if (pick == 2) launch_glds<128, 64, 2, 2, MODE, 3>(p, st);
-  else if (pick == 3) launch_glds<64, 64, 2, 2, MODE, 4>(p, st);
-  else launch_glds<64, 64, 2, 2, MODE, 6>(p, st);
-  return true;
-}
-
-template <typename T, int MODE, bool XF = false>
-void dispatch_igemm(const ConvParams& p, hipStream_t st) {
-  const int N = p.N, M = p.M;
-  auto nblocks = [&](int bp, int bc) { return ((M + bp - 1) / bp) * ((N + bc - 1) / bc); };
-  if (N <= 16) {
-    if (nblocks(256, 16) >= 512) launch_igemm<T, 256, 16, 4, 1, MODE, XF>(p, st);
-    else launch_igemm<T, 64, 16, 4, 1, MODE, XF>(p, st);
-  } else if (N <= 32) {
-    if (nblocks(256, 32) >= 512) launch_igemm<T, 256, 32, 4, 1, MODE, XF>(p, st);
-    else launch_igemm<T, 64, 32, 4, 1, MODE, XF>(p, st);
-  } else if (N <= 64) {
-    if (nblocks(128, 64) >= 384) launch_igemm<T, 128, 64, 2, 2, MODE, XF>(p, st);
-    else launch_igemm<T, 64, 64, 2, 2, MODE, XF>(p, st);
-  } else {
-    if (nblocks(128, 128) >= 384) launch_igemm<T, 128, 128, 2, 2, MODE, XF>(p, st);
-    else if (nblocks(128, 64) >= 384) launch_igemm<T, 128, 64, 2, 2, MODE, XF>(p, st);
-    else launch_igemm<T, 64, 64, 2, 2, MODE, XF>(p, st);
-  }
-}
-
-// dry run (p.plan_splits): report the number of partial images; else check the slab holds them (error flag otherwise)
-thread_local bool g_wgrad_slab_short = false;
-bool wgrad_slab_ok(const WgradParams& p, int parts) {
-  if (p.plan_splits) { *p.plan_splits = parts; return false; }
-  if ((long long)parts * p.Cout * p.J > p.slab_floats) { g_wgrad_slab_short = true; return false; }
-  return true;
-}
-
-template <typename T, int BN, int BJ, int WN, int WJ>
-void launch_wgrad(const WgradParams& p, hipStream_t st) {
-  constexpr int BKM = 8 * Granule<T>::N;
-  WgradParams q = p;
-  q.n_jtiles = (p.J + BJ - 1) / BJ;
-  const int ntiles = (p.Cout + BN - 1) / BN;
-  const int tiles = q.n_jtiles * ntiles;
-  const int steps_total = (p.M + BKM - 1) / BKM;
-  int splits = (1024 + tiles - 1) / tiles;          // aim for ~1024 workgroups
-  int max_splits = (steps_total + 3) / 4;           // at least 4 k-steps per split
-  if (max_splits < 1) max_splits = 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int steps_per = (steps_total + splits - 1) / splits;
-  q.m_chunk = steps_per * BKM;
-  splits = (p.M + q.m_chunk - 1) / q.m_chunk;
-  if (!wgrad_slab_ok(p, splits)) return;
-  const size_t lds = (size_t)(BN + BJ) * 128 * 2;
-  auto kern = conv_wgrad_kernel<T, BN, BJ, WN, WJ>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(tiles, splits), dim3(256), lds, st, q);
-}
-
-template <int BN, int WN, int WJ>
-void launch_wgrad_tr(const WgradParams& p, hipStream_t st) {
-  constexpr int BJ = 128, BKM = 64;
-  WgradParams q = p;
-  q.n_jtiles = (p.J + BJ - 1) / BJ;
-  const int ntiles = (p.Cout + BN - 1) / BN;
-  const int tiles = q.n_jtiles * ntiles;
-  const int steps_total = (p.M + BKM - 1) / BKM;
-  // time ~ (steps/S) * t_step + S * |dW| / (flush rate), t_step ~ 1.6 us measured.  A split's partial image costs a plain
-  // store here (~6 TB/s) and a read by kd6d_grad_acc_resolve at the end of the sweep (~4 TB/s): 2.4 TB/s together (the fp32
-  // atomic flush of rounds 1-3: 1.3 TB/s)
-  //   => S* = sqrt(steps * t_step * rate / |dW|); at most 2 workgroups per CU, because many
-  //   workgroups adding into one small dW are contention-bound (measured: 2048 -> 512 = -25 %)
-  // a caller that keeps several weight gradients in flight asks each for a fraction of the device: fewer,
-  // longer splits -> proportionally fewer atomic tile flushes for the same k-loop work
-  const double frac = (double)p.cu_budget / (double)cached_cu_count();
-  const double dw_bytes = (double)p.Cout * (double)p.J * 4.0;
-  int splits = (int)(frac * sqrt((double)steps_total * 3.8e6 / dw_bytes) + 0.5);
-  if (splits > 512 / tiles) splits = 512 / tiles;
-  if (splits > steps_total / 2) splits = steps_total / 2;
-  if (splits < 1) splits = 1;
-  const int steps_per = (steps_total + splits - 1) / splits;
-  q.m_chunk = steps_per * BKM;
-  splits = (p.M + q.m_chunk - 1) / q.m_chunk;
-  if (!wgrad_slab_ok(p, splits)) return;
-  const size_t stage = (size_t)2 * 2 * BKM * 256;
-  const size_t epi = (size_t)BN * (BJ + 4) * 4;
-  const size_t lds = stage > epi ? stage : epi;
-  auto kern = conv_wgrad_tr_kernel<BN, WN, WJ>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(tiles, splits), dim3(256), lds, st, q);
-}
-
-template <int CG, int NB, int KS>
-void launch_wgrad_small(const WgradParams& p, int R, hipStream_t st) {
-  const int W = p.seg[0].dst_w, H = p.seg[0].dst_h;
-  const int Wp = KS == 3 ? W + 2 : W;
-  const int Qpad = (R * Wp + 31) & ~31;
-  int prow = Qpad + (KS == 3 ? 2 * Wp + 3 : 0) + 8;            // furthest tap of the last position + 8 zero rows
-  const int unit = 64 / CG;                                    // whole 1-KB LDS-DMA bursts
-  prow = (prow + unit - 1) / unit * unit;
-  const int buf_bytes = Qpad * 32 * NB + prow * 16 * CG;
-  const int tiles_per_img = (H + R - 1) / R;
-  const int ntiles = p.batch * tiles_per_img;
-  int grid = 2 * p.cu_budget;                                  // persistent: one flush per workgroup
-  if (grid > ntiles) grid = ntiles;
-  if (!wgrad_slab_ok(p, grid)) return;
-  constexpr int JB_ = (KS * KS * 8 * CG + 15) / 16;
-  const size_t image = (size_t)NB * 16 * JB_ * 16 * sizeof(float);      // the flush's [n][j] image
-  const size_t lds = (size_t)2 * buf_bytes > image ? (size_t)2 * buf_bytes : image;
-  auto kern = conv_wgrad_small_kernel<CG, NB, KS>;
-  static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_lds = lds;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, p, R, tiles_per_img, ntiles, buf_bytes, prow);
-}
-
-// wide, shallow layers: Cin in {8,16,32}, Cout <= 64, 3x3/s1/p1 or 1x1/s1, one level, >= 2^15 pixels, no bias gradient
-bool dispatch_wgrad_small(const WgradParams& p, const kd6d_conv_geom* g, hipStream_t st) {
-  const int force = (int)kd6d_opt(KD6D_OPT_WGRAD_SMALL);
-  if (force == 0 || p.dbias != nullptr || g->nseg != 1 || p.stride != 1) return false;
-  if (!((p.ks == 3 && p.pad == 1) || (p.ks == 1 && p.pad == 0))) return false;
-  if ((p.Cin != 8 && p.Cin != 16 && p.Cin != 32) || p.Cout > 64 || (p.Cout & 7)) return false;
-  const kd6d_seg& q = g->seg[0];
-  if (q.in_row0 != 0 || q.out_row0 != 0 || q.in_w > 256) return false;
-  // measured (tools/bench_conv.py, B = 16): the 1x1 layers gain (64x64 map, 16 -> 8 channels: 16.2 -> 7.5 us); the
-  // 3x3 layers do NOT -- a tile is one DMA round trip of ~3 us for ~0.3 us of MFMA work and the persistent grid
-  // that keeps the atomic flush small also keeps too few round trips in flight (256x256x8->8: 46 -> 45 us,
-  // 128x128x8->16: 26 -> 31, 64x64x8->64: 21 -> 20; more workgroups: slower, the flush serialises).  They stay
-  // on the general kernel unless forced; a deeper DMA ring per workgroup is the open improvement.
-  if (force < 0 && (p.M < (1 << 15) || p.ks != 1)) return false;
-  const int W = q.in_w, H = q.in_h;
-  int R = 512 / W;                     // ~512 positions per tile (256: 9.5 us on the 16 -> 8 layer, 512: 7.5)
-  if (R < 1) R = 1;
-  if (R > H) R = H;
-  const int nb = (p.Cout + 15) / 16;
-  const int cg = p.Cin / 8;
-  auto lds_bytes = [&](int r) {        // as launch_wgrad_small sizes the two buffers
-    const int wp = p.ks == 3 ? W + 2 : W;
-    const int qpad = (r * wp + 31) & ~31;
-    int prow = qpad + (p.ks == 3 ? 2 * wp + 3 : 0) + 8;
-    const int unit = 64 / cg;
-    prow = (prow + unit - 1) / unit * unit;
-    return (size_t)2 * ((size_t)qpad * 32 * nb + (size_t)prow * 16 * cg);
-  };
-  while (R > 1 && lds_bytes(R) > 72 * 1024) R >>= 1;           // two workgroups per CU
-  if (lds_bytes(R) > 144 * 1024) return false;
-#define KD6D_WS_CASE(CG_, NB_, KS_) \
-  if (cg == CG_ && nb == NB_ && p.ks == KS_) { launch_wgrad_small<CG_, NB_, KS_>(p, R, st); return true; }
-  KD6D_WS_CASE(1, 1, 3) KD6D_WS_CASE(1, 2, 3) KD6D_WS_CASE(1, 4, 3)
-  KD6D_WS_CASE(2, 1, 3) KD6D_WS_CASE(2, 2, 3) KD6D_WS_CASE(2, 4, 3)
-  KD6D_WS_CASE(4, 1, 3) KD6D_WS_CASE(4, 2, 3) KD6D_WS_CASE(4, 4, 3)
-  KD6D_WS_CASE(1, 1, 1) KD6D_WS_CASE(2, 1, 1) KD6D_WS_CASE(4, 1, 1)
-  KD6D_WS_CASE(1, 2, 1) KD6D_WS_CASE(2, 2, 1) KD6D_WS_CASE(4, 2, 1)
-  KD6D_WS_CASE(1, 4, 1) KD6D_WS_CASE(2, 4, 1) KD6D_WS_CASE(4, 4, 1)
-#undef KD6D_WS_CASE
+bool launch_glds(const FwdPlan& pl, const ConvParams& q, hipStream_t st) {
+#define KD6D_CASE(bp, bc, wp, wc, ns)                        \
+  if (pl.BP == bp && pl.BC == bc && pl.NSTAGE == ns)         \
+    return launch_kernel<conv_igemm_glds_kernel<bp, bc, wp, wc, MODE, ns>>(dim3(pl.grid_x), pl.threads, pl.lds_bytes, st, q);
+  KD6D_CONV_GLDS_TILES(KD6D_CASE)
+#undef KD6D_CASE
   return false;
 }
 
-void dispatch_wgrad_tr(const WgradParams& p, hipStream_t st) {
-  if (p.Cout <= 16) launch_wgrad_tr<16, 1, 4>(p, st);
-  else if (p.Cout <= 32) launch_wgrad_tr<32, 1, 4>(p, st);
-  else if (p.Cout <= 64) launch_wgrad_tr<64, 1, 4>(p, st);
-  else launch_wgrad_tr<128, 2, 2>(p, st);
+// q.slab: the caller's workspace; the second launch sums the splits and applies the epilogue
+bool launch_splitk(const FwdPlan& pl, const ConvParams& q, hipStream_t st) {
+  bool ok = false;
+#define KD6D_CASE(bp, bc, wp, wc, ns)                                                                          \
+  if (pl.BP == bp && pl.BC == bc && pl.NSTAGE == ns)                                                           \
+    ok = launch_kernel<conv_igemm_glds_kernel<bp, bc, wp, wc, MODE_FWD, ns, true>>(dim3(pl.grid_x, pl.grid_y), pl.threads, \
+                                                                                   pl.lds_bytes, st, q);
+  KD6D_CONV_SPLITK_TILES(KD6D_CASE)
+#undef KD6D_CASE
+  if (ok) hipLaunchKernelGGL(splitk_finalize_kernel, dim3(pl.finalize_grid), dim3(256), 0, st, q, pl.nsplit);
+  return ok;
 }
 
-template <typename T>
-void dispatch_wgrad(const WgradParams& p, hipStream_t st) {
-  if (p.Cout <= 16) launch_wgrad<T, 16, 128, 1, 4>(p, st);
-  else if (p.Cout <= 32) launch_wgrad<T, 32, 128, 1, 4>(p, st);
-  else if (p.Cout <= 64 || p.J <= 64) launch_wgrad<T, 64, 64, 2, 2>(p, st);
-  else launch_wgrad<T, 128, 128, 2, 2>(p, st);
+template <int MODE>
+bool launch_smallc(const FwdPlan& pl, const ConvParams& q, hipStream_t st) {
+#define KD6D_CASE(cg, nb)                                                                                              \
+  if (pl.CG == cg && pl.NB == nb)                                                                                      \
+    return launch_kernel<conv3x3_smallc_kernel<cg, nb, MODE>>(dim3(pl.grid_x), pl.threads, pl.lds_bytes, st, q, pl.halo, \
+                                                              pl.total_rows, pl.patch_bytes, pl.wbytes);
+  KD6D_CONV_SMALLC_TILES(KD6D_CASE)
+#undef KD6D_CASE
+  return false;
 }
 
-}  // namespace
-
-thread_local kd6d_detail::LaunchPlan* kd6d_detail::g_launch_plan = nullptr;
-
-namespace {
-
-// forward dispatch: the per-layer kernel choice
-void dispatch_fwd(const ConvParams& p, const kd6d_conv_geom* g, int dtype, void* workspace, int64_t workspace_bytes,
-                  hipStream_t st) {
-  if (dtype == KD6D_BF16) {
-    if (!dispatch_smallc<MODE_FWD>(p, g, st) && !dispatch_halo_fwd(p, g, st) &&
-        !dispatch_splitk<MODE_FWD>(p, reinterpret_cast<float*>(workspace), (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), st) &&
-        !dispatch_glds<MODE_FWD>(p, st))
-      dispatch_igemm<bf16_t, MODE_FWD>(p, st);
-  } else {
-    dispatch_igemm<float, MODE_FWD>(p, st);
+bool launch_wgrad(const WgradPlan& pl, const WgradParams& p, hipStream_t st) {
+  WgradParams q = p;
+  q.n_jtiles = pl.n_jtiles; q.m_chunk = pl.m_chunk;
+  const dim3 grid(pl.grid_x, pl.grid_y);
+  if (pl.family == kd6d_conv::kWgSmall) {
+#define KD6D_CASE(cg, nb, ks)                                                                                     \
+  if (pl.CG == cg && pl.NB == nb && pl.KS == ks)                                                                  \
+    return launch_kernel<conv_wgrad_small_kernel<cg, nb, ks>>(grid, 256, pl.lds_bytes, st, q, pl.R, pl.tiles_per_img, \
+                                                              pl.ntiles, pl.buf_bytes, pl.prow);
+    KD6D_CONV_WGRAD_SMALL_TILES(KD6D_CASE)
+#undef KD6D_CASE
+  } else if (pl.family == kd6d_conv::kWgTr) {
+#define KD6D_CASE(bn, wn, wj) \
+  if (pl.BN == bn) return launch_kernel<conv_wgrad_tr_kernel<bn, wn, wj>>(grid, 256, pl.lds_bytes, st, q);
+    KD6D_CONV_WGRAD_TR_TILES(KD6D_CASE)
+#undef KD6D_CASE
+  } else if (pl.family == kd6d_conv::kWgGeneric) {
+#define KD6D_CASE(bn, bj, wn, wj) \
+  if (pl.BN == bn && pl.BJ == bj) return launch_kernel<conv_wgrad_kernel<float, bn, bj, wn, wj>>(grid, 256, pl.lds_bytes, st, q);
+    KD6D_CONV_WGRAD_TILES(KD6D_CASE)
+#undef KD6D_CASE
   }
+  return false;
+}
+
+kd6d_conv::Flags plan_flags(const ConvParams& p, int dtype) {
+  kd6d_conv::Flags f;
+  f.dtype = dtype;
+  f.has_stats = p.stats != nullptr; f.stats_groups = p.stats_groups; f.stats_replicas = p.stats_replicas;
+  f.norm_fused = p.norm_dst != nullptr;
+  f.pair_active = pair_bracket_active();
+  return f;
+}
+
+// the per-layer kernel choice (conv_plan.h), launched
+int launch_conv(const FwdPlan& pl, const ConvParams& p, float* workspace, hipStream_t st, const char* who) {
+  ConvParams q = planned_params(p, pl);
+  const bool fwd = pl.mode == MODE_FWD, bf16 = pl.dtype == KD6D_BF16;
+  bool ok = false;
+  switch (pl.family) {
+    case kd6d_conv::kSmallc: ok = fwd ? launch_smallc<MODE_FWD>(pl, q, st) : launch_smallc<MODE_DGRAD>(pl, q, st); break;
+    case kd6d_conv::kHalo: ok = launch_halo(pl, p, st); break;
+    case kd6d_conv::kSplitk: q.slab = workspace; ok = launch_splitk(pl, q, st); break;
+    case kd6d_conv::kGlds: ok = fwd ? launch_glds<MODE_FWD>(pl, q, st) : launch_glds<MODE_DGRAD>(pl, q, st); break;
+    case kd6d_conv::kIgemm:
+      if (pl.XF) ok = bf16 ? launch_igemm<bf16_t, MODE_FWD, true>(pl, q, st) : launch_igemm<float, MODE_FWD, true>(pl, q, st);
+      else if (fwd) ok = bf16 ? launch_igemm<bf16_t, MODE_FWD, false>(pl, q, st) : launch_igemm<float, MODE_FWD, false>(pl, q, st);
+      else ok = bf16 ? launch_igemm<bf16_t, MODE_DGRAD, false>(pl, q, st) : launch_igemm<float, MODE_DGRAD, false>(pl, q, st);
+      break;
+    default: break;
+  }
+  if (!ok) {
+    kd6d_set_error("%s: no kernel is built for the planned variant (family %d)", who, pl.family);
+    return KD6D_ERR_UNSUPPORTED;
+  }
+  return KD6D_OK;
+}
+
+int dispatch_fwd(const ConvParams& p, const kd6d_conv_geom* g, int dtype, bool xf, void* workspace, int64_t workspace_bytes,
+                 hipStream_t st, const char* who) {
+  kd6d_conv::Flags f = plan_flags(p, dtype);
+  f.xf = xf; f.has_workspace = workspace != nullptr; f.ws_bytes = workspace_bytes;
+  const FwdPlan pl = kd6d_conv::plan_fwd(plan_shape(g, p.M, p.N, p.C, p.K), f, plan_options(), cached_cu_count());
+  return launch_conv(pl, p, reinterpret_cast<float*>(workspace), st, who);
 }
 
 int fwd_params(const kd6d_conv_geom* g, int dtype, const char* who, ConvParams& p) {
@@ -1673,25 +1414,21 @@ int fwd_params(const kd6d_conv_geom* g, int dtype, const char* who, ConvParams& 
 }
 
 int set_stats(const kd6d_conv_geom* g, ConvParams& p, kd6d_acc* stats, int stats_groups, const char* who) {
-  KD6D_CHECK_ARG(g->cout % 4 == 0 && stats_groups >= 0, "%s: fused statistics need cout %% 4 == 0", who);
-  KD6D_CHECK_ARG(stats_groups == 0 || (g->cout % stats_groups == 0 && (g->cout / stats_groups) % 4 == 0 &&
-                                       g->cout / stats_groups <= 8),
+  KD6D_CHECK_ARG(kd6d_conv::stats_channels_ok(g->cout) && stats_groups >= 0, "%s: fused statistics need cout %% 4 == 0", who);
+  KD6D_CHECK_ARG(kd6d_conv::stats_groups_ok(g->cout, stats_groups),
                  "%s: fused group statistics need 4 or 8 channels per group (cout=%d, groups=%d)", who, g->cout,
                  stats_groups);
   p.stats = reinterpret_cast<long long*>(stats); p.stats_groups = stats_groups;
   p.stats_skip = 0;
   if (stats_groups > 0) {
     p.stats_cpg_shift = (g->cout / stats_groups) == 8 ? 3 : 2;
-    // the epilogue sums whole 16-row fragments that lie inside one image; a level where that does not hold is left to
-    // stats_followup()
+    // a level the epilogue does not sum is left to stats_followup()
     for (int s2 = 0; s2 < p.nseg; ++s2)
-      if ((p.seg[s2].dst_hw % 16) != 0 || (p.seg[s2].m_begin % 16) != 0) p.stats_skip |= 1 << s2;
+      if (kd6d_conv::stats_level_skipped(p.seg[s2].dst_hw, p.seg[s2].m_begin)) p.stats_skip |= 1 << s2;
   }
   return KD6D_OK;
 }
 
-// Would kd6d_conv2d_fwd_norm take the fused path?  Dry run of the dispatch with the fields that steer it set the way
-// the real call sets them, then the residency rule of kd6d_barrier.h.
 }  // namespace
 
 // The levels the epilogue's group statistics skip (ConvParams::stats_skip): summed from the stored tensor by a small
@@ -1706,40 +1443,14 @@ int kd6d_detail::stats_followup(const ConvParams& p, bool dst_f32, hipStream_t s
 }
 
 namespace {
-bool norm_fusable(const kd6d_conv_geom* g, int dtype, int kind, int groups, ConvParams& p, LaunchPlan& plan) {
-  // option conv.fuse_norm: bit 0 = GroupNorm launches, bit 1 = BatchNorm launches
-  if (((int)kd6d_opt(KD6D_OPT_CONV_FUSE_NORM) & (kind == KD6D_NORM_GROUP ? 1 : 2)) == 0) return false;
+// Would kd6d_conv2d_fwd_norm take the fused path?  Asks the plan (kd6d_conv::norm_fusable); p: the geometry's parameters.
+bool norm_fusable(const kd6d_conv_geom* g, int dtype, int kind, int groups, ConvParams& p) {
   if (fwd_params(g, dtype, "kd6d_conv2d_fwd_norm", p) != KD6D_OK) return false;
-  static float dummy;
-  static kd6d_acc dummy_acc;
-  if (set_stats(g, p, &dummy_acc, kind == KD6D_NORM_GROUP ? groups : 0, "kd6d_conv2d_fwd_norm") != KD6D_OK) return false;
-  if (kind == KD6D_NORM_GROUP && groups <= 0) return false;
-  if (p.stats_skip) return false;       // a level whose statistics need the separate pass: nothing to wait for in-kernel
-  p.norm_dst = &dummy;
-  p.out_f32 = 1;
-  g_launch_plan = &plan;
-  dispatch_fwd(p, g, dtype, nullptr, 0, nullptr);
-  g_launch_plan = nullptr;
-  if (!plan.fused_epilogue || plan.grid <= 0) return false;
-  const int ncu = cached_cu_count();
-  const size_t lds = plan.lds > 0 ? plan.lds : 1;
-  const int waves = plan.threads / 64;
-  if (kind == KD6D_NORM_BATCH) {
-    // grid barrier: every workgroup of the launch pinned until the last one has arrived.  Admit only launches that fit
-    // in HALF of the device's LDS and wave slots (the other half is what window-barrier launches on other streams and
-    // fragmentation may hold), at no more than two workgroups per CU
-    if ((size_t)plan.grid * lds > (size_t)ncu * (160u << 10) / 2) return false;
-    if (plan.grid * waves > ncu * 32 / 2) return false;
-    if (plan.grid > 2 * ncu) return false;
-  } else {
-    // window barrier: with workgroup id == tile id a tile waits for the pixel tiles of its own (level, image) keys only
-    int hw_max = 1;
-    for (int s = 0; s < g->nseg; ++s) hw_max = hw_max > g->seg[s].out_h * g->seg[s].out_w ? hw_max : g->seg[s].out_h * g->seg[s].out_w;
-    const int n_ctiles = (g->cout + 15) / 16;       // upper bound of the channel tiles
-    if (n_ctiles > 16 * KD6D_NORM_MAX_CTILES) return false;
-    (void)hw_max;
-  }
-  return true;
+  int out_hw[kMaxSeg];
+  for (int s = 0; s < p.nseg; ++s) out_hw[s] = p.seg[s].dst_hw;
+  return kd6d_conv::norm_fusable(plan_shape(g, p.M, p.N, p.C, p.K), out_hw, dtype, kind, groups,
+                                 (int)kd6d_opt(KD6D_OPT_CONV_FUSE_NORM), pair_bracket_active(), plan_options(),
+                                 cached_cu_count());
 }
 
 }  // namespace
@@ -1762,7 +1473,8 @@ extern "C" int kd6d_conv2d_fwd(const kd6d_conv_geom* g, int dtype, const void* x
     if (rc) return rc;
   }
   const int pending = kd6d_conv2d_pair_pending();
-  dispatch_fwd(p, g, dtype, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  rc = dispatch_fwd(p, g, dtype, false, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), "kd6d_conv2d_fwd");
+  if (rc) return rc;
   KD6D_CHECK_LAUNCH("kd6d_conv2d_fwd");
   if (p.stats_skip && kd6d_conv2d_pair_pending() == pending) {       // launched (not recorded by a pair bracket)
     rc = stats_followup(p, p.out_f32 || dtype == KD6D_F32, reinterpret_cast<hipStream_t>(stream));
@@ -1788,7 +1500,6 @@ extern "C" int kd6d_conv2d_fwd_block(const kd6d_conv_geom* g, int dtype, const v
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!bn) {
     KD6D_CHECK_ARG(z_out == nullptr, "kd6d_conv2d_fwd_block: z_out without a BatchNorm to apply");
-    dispatch_fwd(p, g, dtype, nullptr, 0, st);
   } else {
     KD6D_CHECK_ARG(bn->sums && bn->gamma && bn->beta && bn->replicas >= 1 && bn->act >= 0 && bn->act <= 2,
                    "kd6d_conv2d_fwd_block: bad BatchNorm description");
@@ -1803,9 +1514,9 @@ extern "C" int kd6d_conv2d_fwd_block(const kd6d_conv_geom* g, int dtype, const v
     p.xf_save_mean = bn->save_mean; p.xf_save_invstd = bn->save_invstd;
     p.xf_running_mean = bn->running_mean; p.xf_running_var = bn->running_var;
     p.xf_z = z_out;
-    if (dtype == KD6D_BF16) dispatch_igemm<bf16_t, MODE_FWD, true>(p, st);
-    else dispatch_igemm<float, MODE_FWD, true>(p, st);
   }
+  rc = dispatch_fwd(p, g, dtype, bn != nullptr, nullptr, 0, st, "kd6d_conv2d_fwd_block");
+  if (rc) return rc;
   KD6D_CHECK_LAUNCH("kd6d_conv2d_fwd_block");
   return KD6D_OK;
 }
@@ -1813,8 +1524,7 @@ extern "C" int kd6d_conv2d_fwd_block(const kd6d_conv_geom* g, int dtype, const v
 extern "C" int kd6d_conv2d_fwd_norm_fusable(const kd6d_conv_geom* g, int dtype, int kind, int groups) {
   if (!g || (kind != KD6D_NORM_GROUP && kind != KD6D_NORM_BATCH)) return 0;
   ConvParams p;
-  LaunchPlan plan;
-  return norm_fusable(g, dtype, kind, groups, p, plan) ? 1 : 0;
+  return norm_fusable(g, dtype, kind, groups, p) ? 1 : 0;
 }
 
 extern "C" int kd6d_conv2d_fwd_norm(const kd6d_conv_geom* g, int dtype, const void* x, const void* w, void* raw_out,
@@ -1826,16 +1536,16 @@ extern "C" int kd6d_conv2d_fwd_norm(const kd6d_conv_geom* g, int dtype, const vo
   KD6D_CHECK_ARG(norm->kind != KD6D_NORM_BATCH || (norm->save_mean && norm->save_invstd),
                  "kd6d_conv2d_fwd_norm: BatchNorm needs save_mean / save_invstd");
   ConvParams p;
-  LaunchPlan plan;
-  if (!norm_fusable(g, dtype, norm->kind, norm->groups, p, plan)) {
+  if (!norm_fusable(g, dtype, norm->kind, norm->groups, p)) {
     kd6d_set_error("kd6d_conv2d_fwd_norm: this geometry does not take the fused path (kd6d_conv2d_fwd_norm_fusable)");
     return KD6D_ERR_UNSUPPORTED;
   }
   unsigned int* timeouts = kd6d_ctx_timeouts_ptr();
   KD6D_CHECK_ARG(timeouts != nullptr, "kd6d_conv2d_fwd_norm: no barrier-timeout counter");
+  int rc = set_stats(g, p, norm->stats, norm->kind == KD6D_NORM_GROUP ? norm->groups : 0, "kd6d_conv2d_fwd_norm");
+  if (rc) return rc;
   p.src = x; p.wgt = w; p.dst = raw_out;
   p.ch_shift = bias; p.act = KD6D_ACT_NONE; p.out_f32 = 1;
-  p.stats = reinterpret_cast<long long*>(norm->stats);
   p.norm_dst = norm->y; p.norm_gamma = norm->gamma; p.norm_beta = norm->beta;
   p.norm_ctr = norm->counters; p.norm_timeouts = timeouts;
   p.norm_eps = norm->eps; p.norm_act = norm->act;
@@ -1849,7 +1559,8 @@ extern "C" int kd6d_conv2d_fwd_norm(const kd6d_conv_geom* g, int dtype, const vo
   } else {
     p.linear_tiles = 1;
   }
-  dispatch_fwd(p, g, dtype, nullptr, 0, reinterpret_cast<hipStream_t>(stream));
+  rc = dispatch_fwd(p, g, dtype, false, nullptr, 0, reinterpret_cast<hipStream_t>(stream), "kd6d_conv2d_fwd_norm");
+  if (rc) return rc;
   KD6D_CHECK_LAUNCH("kd6d_conv2d_fwd_norm");
   return KD6D_OK;
 }
@@ -1870,13 +1581,10 @@ extern "C" int kd6d_conv2d_dgrad(const kd6d_conv_geom* g, int dtype, const void*
   p.src = dy; p.wgt = wt; p.dst = dx;
   p.residual = accumulate ? dx : nullptr;
   p.act = KD6D_ACT_NONE; p.out_f32 = 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == KD6D_BF16) {
-    if (!dispatch_smallc<MODE_DGRAD>(p, g, st) && !dispatch_halo_dgrad(p, g, st) && !dispatch_glds<MODE_DGRAD>(p, st))
-      dispatch_igemm<bf16_t, MODE_DGRAD>(p, st);
-  } else {
-    dispatch_igemm<float, MODE_DGRAD>(p, st);
-  }
+  const FwdPlan pl = kd6d_conv::plan_dgrad(plan_shape(g, p.M, p.N, p.C, p.K), plan_flags(p, dtype), plan_options(),
+                                           cached_cu_count());
+  rc = launch_conv(pl, p, nullptr, reinterpret_cast<hipStream_t>(stream), "kd6d_conv2d_dgrad");
+  if (rc) return rc;
   KD6D_CHECK_LAUNCH("kd6d_conv2d_dgrad");
   return KD6D_OK;
 }
@@ -1899,17 +1607,15 @@ int wgrad_params(const kd6d_conv_geom* g, int dtype, int cu_budget, const char* 
   KD6D_CHECK_ARG(fill_segs(g, false, p.seg, &p.M), "%s: grid too large", who);
   for (int s = 0; s < g->nseg; ++s)
     KD6D_CHECK_ARG(p.seg[s].dst_row0 == p.seg[s].m_begin, "%s: output levels must be packed back to back", who);
-  const int ncu = cached_cu_count();
   KD6D_CHECK_ARG(cu_budget >= 0, "%s: cu_budget=%d", who, cu_budget);
-  p.cu_budget = (cu_budget == 0 || cu_budget > ncu) ? ncu : cu_budget;
+  p.cu_budget = kd6d_conv::clamp_cu_budget(cu_budget, cached_cu_count());
   return KD6D_OK;
 }
-void wgrad_dispatch(const WgradParams& p, const kd6d_conv_geom* g, int dtype, hipStream_t st) {
-  if (dtype == KD6D_BF16) {
-    if (!dispatch_wgrad_small(p, g, st)) dispatch_wgrad_tr(p, st);
-  } else {
-    dispatch_wgrad<float>(p, st);
-  }
+// (the narrow-layer kernel takes no bias gradient)
+WgradPlan wgrad_plan(const WgradParams& p, const kd6d_conv_geom* g, int dtype, bool with_bias) {
+  kd6d_conv::Flags f;
+  f.dtype = dtype; f.with_bias = with_bias;
+  return kd6d_conv::plan_wgrad(plan_shape(g, p.M, p.Cout, p.Cin, p.J), f, plan_options(), cached_cu_count(), p.cu_budget);
 }
 }  // namespace
 
@@ -1917,12 +1623,7 @@ extern "C" int kd6d_conv2d_wgrad_parts(const kd6d_conv_geom* g, int dtype, int w
   WgradParams p;
   int rc = wgrad_params(g, dtype, cu_budget, "kd6d_conv2d_wgrad_parts", p);
   if (rc) return rc;
-  int parts = 0;
-  p.plan_splits = &parts;
-  // (the narrow-layer kernel takes no bias gradient: the same dispatch decision as the real call)
-  static long long dummy_bias;
-  p.dbias = with_bias ? &dummy_bias : nullptr;
-  wgrad_dispatch(p, g, dtype, nullptr);
+  const int parts = wgrad_plan(p, g, dtype, with_bias != 0).parts;
   KD6D_CHECK_ARG(parts >= 1, "kd6d_conv2d_wgrad_parts: no kernel takes this geometry");
   return parts;
 }
@@ -1939,10 +1640,14 @@ extern "C" int kd6d_conv2d_wgrad(const kd6d_conv_geom* g, int dtype, const void*
   p.dw = dw_slab; p.slab_floats = (long long)slab_floats;
   p.dbias = reinterpret_cast<long long*>(dbias); p.acc_hi = (long long)acc_hi_stride;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  g_wgrad_slab_short = false;
-  wgrad_dispatch(p, g, dtype, st);
-  KD6D_CHECK_ARG(!g_wgrad_slab_short, "kd6d_conv2d_wgrad: slab of %lld floats is too small (kd6d_conv2d_wgrad_parts x cout*k*k*cin)",
+  const WgradPlan pl = wgrad_plan(p, g, dtype, dbias != nullptr);
+  KD6D_CHECK_ARG((long long)pl.parts * p.Cout * p.J <= p.slab_floats,
+                 "kd6d_conv2d_wgrad: slab of %lld floats is too small (kd6d_conv2d_wgrad_parts x cout*k*k*cin)",
                  (long long)slab_floats);
+  if (!launch_wgrad(pl, p, st)) {
+    kd6d_set_error("kd6d_conv2d_wgrad: no kernel is built for the planned variant (family %d)", pl.family);
+    return KD6D_ERR_UNSUPPORTED;
+  }
   if (dtype != KD6D_BF16 && dbias) {           // exact-fp32 parity path: separate column-sum pass
     rc = kd6d_detail::colsum_grad_planar(dtype, dy, p.M, g->cout, p.dbias, p.acc_hi, stream);
     if (rc) return rc;

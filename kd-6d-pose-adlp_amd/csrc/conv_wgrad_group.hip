@@ -559,12 +559,7 @@ extern "C" int kd6d_wgrad_group_launch(const void* plan_dev, int n_workgroups, i
                                        void* stream) {
   KD6D_CHECK_ARG(plan_dev && slab_dev && n_workgroups > 0 && n_reduce_blocks > 0, "kd6d_wgrad_group_launch: bad arguments");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_group_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_set = true;
-  }
+  kd6d_raise_lds_limit<wgrad_group_kernel>(kLdsBytes);
   hipLaunchKernelGGL(wgrad_group_kernel, dim3(n_workgroups), dim3(kThreads), kLdsBytes, st,
                      reinterpret_cast<const char*>(plan_dev), slab_dev);
   KD6D_CHECK_LAUNCH("kd6d_wgrad_group_launch");

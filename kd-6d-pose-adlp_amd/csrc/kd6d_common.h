@@ -85,6 +85,18 @@ template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
 
+// Dynamic LDS beyond 64 KB needs the kernel's opt-in.  One memory per kernel FUNCTION (the template argument is the
+// kernel itself, not its type): the largest size set so far, raised when a call needs more -- right both for the
+// kernels whose LDS size is fixed and for those where it grows with the geometry.
+template <auto Kern>
+static inline void kd6d_raise_lds_limit(size_t lds) {
+  static size_t limit = 0;
+  if (lds > limit) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    limit = lds;
+  }
+}
+
 // 16-byte granule: 8 bf16 or 4 f32.
 template <typename T> struct Granule;
 template <> struct Granule<bf16_t> { static constexpr int N = 8; };

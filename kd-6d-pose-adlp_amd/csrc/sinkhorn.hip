@@ -392,12 +392,7 @@ extern "C" int kd6d_sinkhorn_div_fwd_bwd(const float* xs, const float* alpha, co
                  "kd6d_sinkhorn_div_fwd_bwd: need blur>0 and 0<scaling<1");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t lds = sizeof(WaveLds) * kWaves + sizeof(float) * kWaves * 5;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_small_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  kd6d_raise_lds_limit<sinkhorn_small_kernel>(lds);
   // option sinkhorn.lanes = 0: every set on the general (one softmin after the other) path (tests)
   const int slow = kd6d_opt(KD6D_OPT_SINKHORN_LANES) == 0;
   hipLaunchKernelGGL(sinkhorn_small_kernel, dim3(n_images), dim3(64 * kWaves), lds, st, xs, alpha,

@@ -112,6 +112,10 @@ CONV_CASES = [
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_fwd_plain(gpu_device, dtype, case):
+    _check_conv_fwd_plain(gpu_device, dtype, case)
+
+
+def _check_conv_fwd_plain(gpu_device, dtype, case):
     ops = _ops()
     B, Cin, Cout, k, stride, levels = case
     g = torch.Generator().manual_seed(B * 1000 + Cin * 7 + Cout)
@@ -320,6 +324,10 @@ def test_conv_wgrad(gpu_device, dtype, case):
     (2, 8, 8, 3, [(3, 300)]),          # wider than 256: stays on the general kernel
 ])
 def test_conv_wgrad_small_layers(gpu_device, case):
+    _check_conv_wgrad_small(gpu_device, case)
+
+
+def _check_conv_wgrad_small(gpu_device, case):
     ops = _ops()
     _option("wgrad.small", 1)
     dtype = torch.bfloat16
@@ -1296,11 +1304,16 @@ def test_conv_block_bn_on_load(gpu_device, dtype, case):
     batch sums, then kd6d_conv2d_fwd): the activation B writes on the way must be what bn_train_fwd stores, B's conv
     output and batch sums what the convolution of that tensor gives, and A's save_mean / save_invstd / running statistics
     must be the ones the separate launch leaves."""
-    ops = _ops()
-    dev = gpu_device
     B, C0, C1, k1, C2, k2, (H, W) = case
     if dtype == torch.float32 and B * H * W > 20000:
         pytest.skip("fp32 mode: covered by the smaller cases")
+    _check_conv_block_bn_on_load(gpu_device, dtype, case)
+
+
+def _check_conv_block_bn_on_load(gpu_device, dtype, case):
+    ops = _ops()
+    dev = gpu_device
+    B, C0, C1, k1, C2, k2, (H, W) = case
     gen = torch.Generator().manual_seed(C0 + 3 * C1 + 7 * C2)
     R = ops.BN_REPLICAS
     ga = ops.Geom(B, C0, C1, k1, 1, k1 // 2, [(H, W)])
@@ -1347,6 +1360,24 @@ def test_conv_block_bn_on_load(gpu_device, dtype, case):
     torch.testing.assert_close(raw_b, raw_ref, rtol=5e-3, atol=5e-3)       # a few inputs one bf16 rounding step apart
     torch.testing.assert_close(_acc_val(sums_b, R * 2 * C2).view(R, 2 * C2).sum(0), _acc_val(sums_ref, 2 * C2),
                                rtol=1e-3, atol=0.5)
+
+
+def test_lds_opt_in_grows_within_one_process(gpu_device):
+    """A kernel's dynamic-LDS limit (kd6d_raise_lds_limit) is remembered per kernel and raised when a later call of the same
+    kernel needs more.  Each pair below runs one kernel variant twice, the second time with more LDS; a launch beyond the
+    limit set so far would fail with a launch error.  Values against the references of the neighbouring tests."""
+    bf16 = torch.bfloat16
+    # BatchNorm on load, 16 x 64 x 64 pixels, C1 -> 128 channels, 1x1: 512 x 1 tiles of 128 x 128 on the register-staged
+    # kernel, 64 KB + 8 * C1 bytes of LDS
+    for C1 in (64, 256):
+        _check_conv_block_bn_on_load(gpu_device, bf16, (16, 16, C1, 1, 128, 1, (64, 64)))
+    # resident-patch kernel, 3x3, 8 -> 8 channels: the patch grows with the halo (map width + 1 rows on either side)
+    _option("conv.smallc", 1)
+    for side in (64, 256):
+        _check_conv_fwd_plain(gpu_device, bf16, (1, 8, 8, 3, 1, [(side, side)]))
+    # narrow weight gradient, 1x1, 16 -> 8 channels
+    for W in (64, 256):
+        _check_conv_wgrad_small(gpu_device, (1, 16, 8, 1, [(64, W)]))
 
 
 @pytest.mark.parametrize("blur", [0.05, 0.001])
