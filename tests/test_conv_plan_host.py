@@ -10,7 +10,6 @@ header the launchers include (through tests/conv_plan_host.cpp).  libkd6d.so is 
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 import pytest
@@ -19,91 +18,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
 import step_layers  # noqa: E402
 
-LL = ctypes.c_longlong
-NCU = 256
-BF16, F32 = 0, 1
-SMALLC, HALO, SPLITK, GLDS, IGEMM = range(5)
-WG_SMALL, WG_TR, WG_GENERIC = range(3)
-CONV_FIELDS = ("family BP BC WP WC NSTAGE HMAX CG NB PDB NORM XF grid_x grid_y threads lds n_ctiles n_ptiles p_fastest nk_split "
-               "nsplit finalize_grid halo total_rows patch_bytes wbytes fused_epilogue").split()
-WGRAD_FIELDS = "family BN BJ WN WJ CG NB KS parts m_chunk n_jtiles grid_x grid_y lds R tiles_per_img ntiles buf_bytes prow".split()
-OPT_NAMES = ("halo", "halo_pairing", "halo_wide", "smallc", "smallc_wmax", "splitk", "tile", "wgrad_small")
-OPT_DEFAULT = dict(halo=-1, halo_pairing=1, halo_wide=1, smallc=-1, smallc_wmax=640, splitk=-1, tile=-1, wgrad_small=-1)
-WS_BYTES = 64 << 20          # the split-K workspace of tools/bench_conv.py
-
-
-class Plan(dict):
-    __getattr__ = dict.__getitem__
+from conv_plan_lib import (BF16, F32, GLDS, HALO, IGEMM, LISTS, NCU, OPT_DEFAULT, SMALLC, SPLITK, WG_GENERIC, WG_SMALL,  # noqa: E402
+                           WG_TR, WS_BYTES, Layer, build_lib, fusable, plan_conv, plan_wgrad)
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("conv_plan") / "libconvplan.so")
-    subprocess.check_call(["g++", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so, os.path.join(HERE, "conv_plan_host.cpp")])
-    return ctypes.CDLL(so)
-
-
-def _ints(v):
-    return (ctypes.c_int * len(v))(*v)
-
-
-_OPTS = {}
-
-
-def _opts(o):
-    key = tuple(sorted(o.items()))
-    if key not in _OPTS:
-        _OPTS[key] = _ints([dict(OPT_DEFAULT, **o)[n] for n in OPT_NAMES])
-    return _OPTS[key]
-
-
-class Layer:
-    """One convolution over a pyramid of input levels, packed back to back as kd6d.ops.Geom packs them."""
-
-    def __init__(self, batch, cin, cout, k, stride, levels, out_shift=0):
-        self.batch, self.cin, self.cout, self.k, self.stride, self.pad = batch, cin, cout, k, stride, k // 2
-        self.levels = [tuple(l) for l in levels]
-        self.out = [((h + 2 * self.pad - k) // stride + 1, (w + 2 * self.pad - k) // stride + 1) for h, w in self.levels]
-        self.seg, rin, rout = [], 0, out_shift
-        for (h, w), (ho, wo) in zip(self.levels, self.out):
-            self.seg += [h, w, rin, rout]
-            rin += batch * h * w
-            rout += batch * ho * wo
-        self.rows_in, self.rows_out = rin, rout - out_shift
-        self.out_hw = [ho * wo for ho, wo in self.out]
-        self.wmax = max(w for _, w in self.levels)
-        self._shape = {}
-
-    def shape(self, kind):
-        kind = "dgrad" if kind == "dgrad" else "fwd"
-        if kind not in self._shape:
-            self._shape[kind] = self._make_shape(kind)
-        return self._shape[kind]
-
-    def _make_shape(self, kind):
-        taps = self.k * self.k
-        if kind == "dgrad":
-            head = [self.rows_in, self.cin, self.cout, taps * self.cout]
-        else:
-            head = [self.rows_out, self.cout, self.cin, taps * self.cin]
-        return _ints(head + [self.k, self.stride, self.pad, self.batch, len(self.levels)] + self.seg)
-
-
-def plan_conv(lib, layer, kind="fwd", dtype=BF16, stats=0, groups=0, replicas=0, norm=0, xf=0, ws=0, pair=0, **opts):
-    out = (LL * len(CONV_FIELDS))()
-    lib.cp_plan_conv(layer.shape(kind), _ints([dtype, stats, groups, replicas, norm, xf, ws, pair]), LL(WS_BYTES if ws else 0),
-                     _opts(opts), NCU, int(kind == "dgrad"), out)
-    return Plan(zip(CONV_FIELDS, out))
-
-
-def plan_wgrad(lib, layer, dtype=BF16, bias=0, budget=0, **opts):
-    out = (LL * len(WGRAD_FIELDS))()
-    lib.cp_plan_wgrad(layer.shape("wgrad"), dtype, bias, _opts(opts), NCU, budget, out)
-    return Plan(zip(WGRAD_FIELDS, out))
-
-
-def fusable(lib, layer, dtype, kind, groups, fuse_norm=3, pair=0, **opts):
-    return lib.cp_norm_fusable(layer.shape("fwd"), _ints(layer.out_hw), dtype, kind, groups, fuse_norm, pair, _opts(opts), NCU)
+    return build_lib(tmp_path_factory.mktemp("conv_plan"))
 
 
 def _ceil(a, b):
@@ -263,9 +184,6 @@ def _check_wgrad(p, layer, dtype, bias, opts, seen):
         assert p.parts * p.m_chunk >= M > (p.parts - 1) * p.m_chunk and p.grid_y == p.parts, what
         assert p.grid_x == p.n_jtiles * _ceil(layer.cout, p.BN) and p.n_jtiles * p.BJ >= layer.k ** 2 * layer.cin, what
         seen["wgrad_tr" if dtype == BF16 else "wgrad"].add((p.BN, p.WN, p.WJ, 0, 0, 0) if dtype == BF16 else (p.BN, p.BJ, p.WN, p.WJ, 0, 0))
-
-
-LISTS = ("igemm", "glds", "splitk", "smallc", "halo", "halo_norm", "wgrad", "wgrad_tr", "wgrad_small")
 
 
 def test_invariants_of_every_plan_over_a_sweep(lib):
