@@ -289,6 +289,7 @@ int kd6d_device_cu_count(void);
  *                  evaluated exactly in the difference form | 0 every pair in the difference form
  *   sinkhorn.dense_rows  rows per workgroup of the dense matrix-pipe softmins (each workgroup streams all columns through
  *                  LDS): -1 = 128 from 8192 rows up, 64 below | 64 | 128
+ *   stem.fused      1 | 0 kd6d_bn_pool_bwd_wgrad_parts reports 0: the apply pass and the weight gradient stay two launches
  * Unknown names return KD6D_ERR_ARG. */
 /* Context: the library's mutable state -- the option table, the pair bracket of kd6d_conv2d_pair_begin/_end and the
  * counter of in-kernel barrier waits that gave up -- lives in a kd6d_ctx.  Every entry point of this header acts on the
@@ -380,6 +381,28 @@ int kd6d_bn_pool_train_bwd(int dtype, int x_f32, const void* x, const void* dy, 
                            int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
                            int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat, unsigned int* counter, float* dgamma,
                            float* dbeta, int replicas, void* stream);
+
+/* A pooled block whose INPUT needs no gradient (the first block of a network: its input is the image): the gradient
+ * of the convolution output is read by the weight gradient alone, so it is never stored.
+ * kd6d_bn_pool_train_bwd_reduce: the reduction pass of kd6d_bn_pool_train_bwd alone -- the two sums, into `replicas`
+ * rows.  kd6d_bn_pool_bwd_wgrad: the apply pass and the weight gradient of the convolution in front as ONE launch.  It
+ * re-derives the windows from raw (fp32 convolution output, (B,H,W,cout)) exactly as kd6d_bn_pool_train_bwd does, forms
+ * the gradient of raw in registers, rounds it to bf16 as the stored tensor was, and contracts it with x (the block's
+ * input, (B,H,W,cin) bf16) in fp32: the products of the separate path, another association of their sum.  dgamma /
+ * dbeta (optional): += the totals, one writer per channel.  The weight gradient arrives as partial images in dw_slab,
+ * laid out as kd6d_conv2d_wgrad's (dw_slab + s * cout*9*cin, every element of every part written, no atomics: two
+ * executions give the same bits); kd6d_bn_pool_bwd_wgrad_parts() tells how many for a geometry, dtype and cu_budget
+ * -- or 0 when the geometry is not taken: 3x3 / stride 1 / pad 1, cin = 8, cout = 8 or 16, one level packed from row
+ * 0 with even H and W <= 256, bf16 (csrc/conv_plan.h, stem_bwd_rule); option stem.fused = 0 makes it report 0 for
+ * every geometry.  cu_budget as in kd6d_conv2d_wgrad. */
+int kd6d_bn_pool_train_bwd_reduce(int dtype, int x_f32, const void* x, const void* dy, int B, int H, int W, int C,
+                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                  int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat, int replicas, void* stream);
+int kd6d_bn_pool_bwd_wgrad_parts(const kd6d_conv_geom* g, int dtype, int cu_budget);
+int kd6d_bn_pool_bwd_wgrad(const kd6d_conv_geom* g, int dtype, const void* x, const float* raw, const void* dz,
+                           const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
+                           const kd6d_acc* sum_dy, const kd6d_acc* sum_dy_xhat, int replicas, float* dgamma,
+                           float* dbeta, float* dw_slab, int64_t slab_floats, int cu_budget, void* stream);
 
 #define KD6D_BARRIER_WORDS 32
 /* BN backward as ONE launch (also kd6d_bn_pool_train_bwd, and kd6d_gn_relu_bwd below): when `counter`

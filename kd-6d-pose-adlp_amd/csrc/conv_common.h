@@ -821,6 +821,7 @@ static inline kd6d_conv::Options plan_options() {
   o.halo_wide = (int)kd6d_opt(KD6D_OPT_CONV_HALO_WIDE); o.smallc = (int)kd6d_opt(KD6D_OPT_CONV_SMALLC);
   o.smallc_wmax = (int)kd6d_opt(KD6D_OPT_CONV_SMALLC_WMAX); o.splitk = (int)kd6d_opt(KD6D_OPT_CONV_SPLITK);
   o.tile = (int)kd6d_opt(KD6D_OPT_CONV_TILE); o.wgrad_small = (int)kd6d_opt(KD6D_OPT_WGRAD_SMALL);
+  o.stem_fused = (int)kd6d_opt(KD6D_OPT_STEM_FUSED);
   return o;
 }
 // the launch's copy of the parameters with the planned fields in

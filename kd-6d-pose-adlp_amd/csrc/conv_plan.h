@@ -41,6 +41,7 @@ struct Flags {
 };
 struct Options {                   // kd6d_set_option values (kd6d_common.h)
   int halo = -1, halo_pairing = 1, halo_wide = 1, smallc = -1, smallc_wmax = 640, splitk = -1, tile = -1, wgrad_small = -1;
+  int stem_fused = 1;
 };
 
 // ---- kernel variants: the one list of each family; the launchers expand their instantiations from these ----------
@@ -95,6 +96,13 @@ struct WgradPlan {
   int parts = 0, m_chunk = 0, n_jtiles = 0, grid_x = 0, grid_y = 1;
   long long lds_bytes = 0;
   int R = 0, tiles_per_img = 0, ntiles = 0, buf_bytes = 0, prow = 0;      // small
+};
+// BatchNorm + max-pool backward fused into the weight gradient (stem_bwd.hip): a block whose input needs no gradient
+struct StemBwdPlan {
+  int NOUT = 0;                            // the variant: result channels, 8 or 16
+  int R = 0, tiles_per_img = 0, ntiles = 0, Qpad = 0, prow = 0, tiles_per_wg = 0;
+  int grid = 0, parts = 0;                 // workgroups = partial dW images
+  long long lds_bytes = 0, slab_floats = 0;
 };
 
 // ---- shared arithmetic -----------------------------------------------------------------------------------------
@@ -525,6 +533,48 @@ inline void wgrad_tr_rule(const Shape& p, int ncu, int cu_budget, WgradPlan& pl)
   if (splits < 1) splits = 1;
   wgrad_split(pl, p, tiles, splits, steps_total, BKM);
   pl.lds_bytes = wgrad_tr_lds(pl.BN);
+}
+
+// The first block of the darknet-tiny students: 3x3/s1/p1, 8 stored source channels, 8 or 16 result channels, one level
+// packed from row 0, train-mode BatchNorm + activation + 2x2 max-pool behind it and NO data gradient wanted.  There the
+// gradient of the convolution output is read by the weight gradient alone, so one kernel forms it in LDS from the
+// convolution output and the pooled gradient and contracts it with the source patch at once (kd6d_bn_pool_bwd_wgrad).
+// A tile is R whole image rows (R even: whole pool windows) of at most 512 pixels; workgroup s walks the T consecutive
+// tiles s*T ... and stores one partial image, every (channel, tap) block accumulated over 32-pixel steps in pixel order.
+// T comes from the pixel split of the transposing kernel (wgrad_tr_rule) this launch stands in for: where that split is
+// a whole number of tiles of whole 32-pixel steps (the students' stems: 2048 pixels = 4 tiles of 2 x 256, 512 parts) the
+// partial images are the SAME sums in the SAME association as the separate path's, bit for bit; elsewhere another valid
+// association of the same products.  cu_budget: clamp_cu_budget().  Option stem.fused = 0 turns the rule off.
+inline bool stem_bwd_rule(const Shape& p, const Flags& f, bool need_dx, const Options& o, int ncu, int cu_budget,
+                          StemBwdPlan& pl) {
+  if (o.stem_fused == 0 || need_dx || f.dtype != kBf16 || f.with_bias || p.nseg != 1) return false;
+  if (p.ks != 3 || p.stride != 1 || p.pad != 1 || p.C != 8 || (p.N != 8 && p.N != 16)) return false;
+  const Level& q = p.seg[0];
+  const int W = q.in_w, H = q.in_h;
+  if (q.in_row0 != 0 || q.out_row0 != 0 || W < 2 || H < 2 || (W & 1) || (H & 1) || W > 256) return false;
+  StemBwdPlan t;
+  t.NOUT = p.N;
+  t.R = (512 / W) & ~1;                   // (W <= 256: at least 2)
+  if (t.R > H) t.R = H;
+  const int Wp = W + 2;
+  t.Qpad = (t.R * W + 31) & ~31;          // pixels of a tile, whole 32-pixel steps (the tail: zero gradient rows)
+  // patch rows: the furthest tap of the last (tail) pixel + 8 zero rows, whole 1-KB LDS-DMA bursts
+  t.prow = (((t.Qpad - 1) / W + 3) * Wp + 3 + 8 + 63) / 64 * 64;
+  t.tiles_per_img = ceil_div(H, t.R);
+  t.ntiles = p.batch * t.tiles_per_img;
+  WgradPlan tr;
+  wgrad_tr_rule(p, ncu, cu_budget, tr);
+  t.tiles_per_wg = tr.m_chunk / (t.R * W);
+  if (t.tiles_per_wg < 1) t.tiles_per_wg = 1;
+  t.grid = ceil_div(t.ntiles, t.tiles_per_wg);
+  t.parts = t.grid;
+  // the two per-channel totals, the gradient tile (2 bytes x NOUT per pixel), the source patch; or the flush's image
+  const long long tile = 128 + (long long)t.Qpad * 2 * t.NOUT + (long long)t.prow * 16;
+  const long long image = 16ll * 80 * 4;
+  t.lds_bytes = tile > image ? tile : image;
+  t.slab_floats = (long long)t.parts * p.N * p.K;
+  pl = t;
+  return true;
 }
 
 // fp32 (exact-parity path): the generic kernel

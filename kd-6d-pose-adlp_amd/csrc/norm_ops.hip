@@ -1753,6 +1753,26 @@ extern "C" int kd6d_bn_pool_train_bwd(int dtype, int x_f32, const void* x, const
   return KD6D_OK;
 }
 
+// the reduction pass alone: the caller finishes with kd6d_bn_pool_bwd_wgrad (stem_bwd.hip), which never stores dx
+extern "C" int kd6d_bn_pool_train_bwd_reduce(int dtype, int x_f32, const void* x, const void* dy, int B, int H, int W,
+                                             int C, const float* mean, const float* invstd, const float* gamma,
+                                             const float* beta, int act, kd6d_acc* sum_dy, kd6d_acc* sum_dy_xhat,
+                                             int replicas, void* stream) {
+  Prep p;
+  int rc = check_pool(dtype, B, H, W, C, stream, "kd6d_bn_pool_train_bwd_reduce", &p);
+  if (rc) return rc;
+  KD6D_CHECK_ARG(replicas >= 1 && replicas <= 64, "kd6d_bn_pool_train_bwd_reduce: replicas=%d outside [1,64]", replicas);
+  KD6D_CHECK_ARG(x && dy && mean && invstd && gamma && beta && sum_dy && sum_dy_xhat,
+                 "kd6d_bn_pool_train_bwd_reduce: null pointer");
+  const int items = (int)p.ngran;
+  DISPATCH_TTX(dtype, x_f32,
+               hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<T_, TX_>), dim3(bn_pool_bwd_reduce_grid(items)), dim3(kThreads),
+                                   kFlushLdsBytes, p.st, (const TX_*)x, (const T_*)dy, items, H, W, C, mean, invstd, gamma,
+                                   beta, act, words(sum_dy), words(sum_dy_xhat), replicas));
+  KD6D_CHECK_LAUNCH("kd6d_bn_pool_train_bwd_reduce");
+  return KD6D_OK;
+}
+
 extern "C" int kd6d_gn_relu_fwd(int dtype, int x_f32, const void* x, void* y, const int32_t* level_hw_host,
                                 int nseg, int batch, int C, int groups, const float* gamma,
                                 const float* beta, float eps, kd6d_acc* stats, int flags, void* stream) {

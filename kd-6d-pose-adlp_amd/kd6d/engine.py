@@ -291,6 +291,18 @@ class Conv:
             parts = self._parts[key] = ops.conv2d_wgrad_parts(g, dtype, self.b is not None, cu_budget)
         return self.net.store.slab(self.w, parts)
 
+    def stem_slab(self, g, dtype):
+        """The slab of the fused pooled-BatchNorm backward + weight gradient (ops.bn_pool_bwd_wgrad), or None when that
+        launch does not take this geometry (or option stem.fused = 0).  Sized for PoseNet.wgrad_budget(), the budget of
+        the separate launch it stands in for: the fused launch splits the pixels as that one does (csrc/conv_plan.h,
+        stem_bwd_rule)."""
+        budget = self.net.wgrad_budget()
+        key = (id(g), dtype, "stem", budget, ops.get_option("stem.fused"))
+        parts = self._parts.get(key)
+        if parts is None:
+            parts = self._parts[key] = ops.bn_pool_bwd_wgrad_parts(g, dtype, budget) if self.b is None else 0
+        return self.net.store.slab(self.w, parts) if parts else None
+
     def bwd(self, x, dy, batch, levels, need_dx=True, dx=None, accumulate=False, need_dw=True):
         """wgrad (+ bias grad) into the flat grad buffer, then dgrad."""
         st = self.net.store
@@ -304,17 +316,19 @@ class Conv:
             grp.add(g, x, dy, st.storage(self.w, "grads"), None if self.b is None else st.storage(self.b, "grads"),
                     flops=self.flops(g))
         elif (side := self.net.next_side_stream()) is None:
-            ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, 0), flops=self.flops(g),
-                             dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride)
+            budget = self.net.wgrad_budget()         # (0: the device)
+            ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
+                             dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride, cu_budget=budget)
         else:
             # the weight gradient feeds nothing in the reverse sweep: fork it onto the side stream so it
             # overlaps the dgrad / normalisation chain (both under-fill 256 CUs at these layer sizes);
             # PoseNet.backward joins before the gradient exchange.  x and dy are per-layer buffers.
+            budget = self.net.wgrad_budget()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, self.net.wgrad_cu_budget), flops=self.flops(g),
+                ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
                                  dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride,
-                                 cu_budget=self.net.wgrad_cu_budget)
+                                 cu_budget=budget)
         if not need_dx:
             return None
         return ops.conv2d_dgrad(g, dy, self.weight_t(), dx=dx, accumulate=accumulate, flops=self.flops(g))
@@ -459,6 +473,18 @@ class ConvBlock:
         o = (2 * A + 2) * c
         w1, w2 = s[o:o + A * R * c], s[o + A * R * c:o + 2 * A * R * c]
         counter = s[o + 2 * A * R * c:o + 2 * A * R * c + ops.BARRIER_WORDS]      # zeroed with the arena at the start of the step
+        if pooled is not None and not need_dx and x.dtype == torch.bfloat16:
+            # nothing but the weight gradient reads the gradient of the convolution output: formed in LDS, never stored
+            g = self.conv.geom(batch, levels)
+            slab = self.conv.stem_slab(g, x.dtype)
+            if slab is not None:
+                gamma, beta = st.storage(self.bn.gamma), st.storage(self.bn.beta)
+                ops.bn_pool_train_bwd_reduce(raw, dz, batch, pooled[0], pooled[1], mean, invstd, gamma, beta, ACT_LEAKY,
+                                             w1, w2, replicas=R)
+                ops.bn_pool_bwd_wgrad(g, x, raw, dz, mean, invstd, gamma, beta, ACT_LEAKY, w1, w2,
+                                      st.storage(self.bn.gamma, "grads"), st.storage(self.bn.beta, "grads"), slab,
+                                      replicas=R, flops=self.conv.flops(g), cu_budget=net.wgrad_budget())
+                return None
         draw = net.buf(self.name + ".draw", raw.shape, net.dtype)
         if pooled is not None:                  # dz is the gradient of the pooled output
             ops.bn_pool_train_bwd(raw, dz, draw, batch, pooled[0], pooled[1], mean, invstd, st.storage(self.bn.gamma),
@@ -719,6 +745,12 @@ class PoseNet:
 
     def fuse_norm_on(self):
         return False if self.fuse_norm is None else bool(self.fuse_norm)
+
+    def wgrad_budget(self):
+        """CU budget of a per-layer weight-gradient launch (ops.conv2d_wgrad, ops.bn_pool_bwd_wgrad): the share
+        wgrad_cu_budget when these launches are forked onto side streams (next_side_stream() gives one), the whole
+        device (0) when they run on the main stream.  The one place that decides it: slab sizes and launches agree."""
+        return self.wgrad_cu_budget if (self.side_streams or self.side_stream is not None) else 0
 
     def next_side_stream(self):
         if self.side_streams:

@@ -487,6 +487,41 @@ def bn_pool_train_bwd(x, dy, dx, batch, h, w, mean, invstd, gamma, beta, act, ws
     return dx
 
 
+def bn_pool_train_bwd_reduce(x, dy, batch, h, w, mean, invstd, gamma, beta, act, ws_sum_dy, ws_sum_dy_xhat, replicas=1):
+    """The reduction pass of bn_pool_train_bwd alone: the two sums into `replicas` rows (bn_pool_bwd_wgrad finishes)."""
+    rows, c = x.shape
+    assert rows == batch * h * w and tuple(dy.shape) == (batch * (h // 2) * (w // 2), c)
+    assert ws_sum_dy.numel() >= replicas * c * ACC_FLOATS and ws_sum_dy_xhat.numel() >= replicas * c * ACC_FLOATS
+    check(lib.kd6d_bn_pool_train_bwd_reduce(dt_code(dy.dtype), _xf32(x, dy.dtype), _ptr(x), _ptr(dy), batch, h, w, c,
+                                            _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), act, _ptr(ws_sum_dy),
+                                            _ptr(ws_sum_dy_xhat), replicas, _stream()), "kd6d_bn_pool_train_bwd_reduce")
+
+
+def bn_pool_bwd_wgrad_parts(geom, dtype, cu_budget=0):
+    """Partial dW images kd6d_bn_pool_bwd_wgrad writes for this geometry / budget; 0: the fused launch does not take it."""
+    n = int(lib.kd6d_bn_pool_bwd_wgrad_parts(geom.ref, dt_code(dtype), int(cu_budget)))
+    if n < 0:
+        check(n, "kd6d_bn_pool_bwd_wgrad_parts")
+    return n
+
+
+def bn_pool_bwd_wgrad(geom, x, raw, dz, mean, invstd, gamma, beta, act, ws_sum_dy, ws_sum_dy_xhat, dgamma, dbeta, dw_slab,
+                      replicas=1, flops=0, cu_budget=0):
+    """Apply pass of the pooled BatchNorm backward + weight gradient of the convolution in front, one launch, for a block
+    whose input needs no gradient.  x: the block's input (rows, cin); raw: fp32 conv output (rows, cout); dz: gradient of
+    the pooled output; the sums as bn_pool_train_bwd_reduce left them; dw_slab: fp32 (bn_pool_bwd_wgrad_parts, cout*9*cin)."""
+    assert geom.ksize == 3 and x.shape == (geom.rows_in, geom.cin) and raw.shape == (geom.rows_out, geom.cout)
+    assert raw.dtype == torch.float32 and x.dtype == dz.dtype and dz.numel() * 4 == raw.numel()
+    assert dw_slab.dtype == torch.float32 and dw_slab.is_contiguous()
+    assert ws_sum_dy.numel() >= replicas * geom.cout * ACC_FLOATS and ws_sum_dy_xhat.numel() >= replicas * geom.cout * ACC_FLOATS
+    with _Timed("conv_wgrad", flops, geom):
+        check(lib.kd6d_bn_pool_bwd_wgrad(geom.ref, dt_code(x.dtype), _ptr(x), _ptr(raw), _ptr(dz), _ptr(mean), _ptr(invstd),
+                                         _ptr(gamma), _ptr(beta), act, _ptr(ws_sum_dy), _ptr(ws_sum_dy_xhat), replicas,
+                                         _ptr(dgamma), _ptr(dbeta), _ptr(dw_slab), dw_slab.numel(), int(cu_budget),
+                                         _stream()), "kd6d_bn_pool_bwd_wgrad")
+    return dw_slab
+
+
 def _hw_array(level_hw):
     arr = (ctypes.c_int32 * len(level_hw))(*[int(v) for v in level_hw])
     return arr
