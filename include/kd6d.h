@@ -596,6 +596,28 @@ int kd6d_pose_remap(int n_inst, int n_images, int n_class, const int32_t* inst_i
 int kd6d_pose_errors(int n_problems, int max_v, const float* verts, const int32_t* voff, const int32_t* vcnt,
                      const int32_t* vidx, const float* K, const float* Rg, const float* Tg, const float* Rp,
                      const float* Tp, const int32_t* sym, float* err, int32_t* nn, void* stream);
+/* ---- BOP pose errors on the device (csrc/bop_err.hip; added under ABI 11, new symbols only): MSSD and MSPD of
+ * n_problems (ground truth, prediction) pairs.  Problem p scores ALL vcnt[p] vertices v_i = verts[voff[p] + i] (no cap,
+ * no index table) under the symmetry transforms S_s = syms[soff[p] + s], s < scnt[p] (12 floats each: R row-major, then
+ * t; scnt[p] <= 0: the identity alone, syms is then not read for p):
+ *   err[p][0] = min_s max_i |(Rp v_i + Tp) - (Rg (S_s v_i) + Tg)|                           (mssd, the vertices' unit)
+ *   err[p][1] = the same min / max over the pinhole projections q.xy / (q.z + 1e-8), q = K x  (mspd, pixels)
+ * K, Rg, Rp (P, 9), Tg, Tp (P, 3) per problem.  Rg S_R and Rg S_t are composed once per (problem, symmetry);
+ * differences are formed as (Rg S_R) v + (Rg S_t + (Tg - Tp)) - Rp v, in fp32.  vcnt[p] <= 0 gives err = {0, 0}.
+ * Two launches: the maximum of every (problem, symmetry) goes to `workspace`, row p holding
+ * cap = workspace_floats / (2 n_problems) symmetries; the second launch takes the minima.  A scnt[p] above cap is
+ * clamped to cap: size the workspace with kd6d_bop_errors_workspace_floats(n_problems, the largest scnt).
+ * n_problems == 0 returns success without a launch and reads no pointer.  The caller guarantees that every vertex and
+ * symmetry index lies inside its pool (kd6d.ops.bop_errors checks it).
+ * Bitwise property: max and min of floats are exact in any order -- no atomics, no accumulators, no in-kernel
+ * cross-workgroup barrier.  err[p] is a pure function of problem p's own inputs: two launches agree bit for bit, a
+ * problem scores the same alone and inside any batch, under any order of its vertices and any order of its symmetries;
+ * a duplicated symmetry changes nothing and an added one can only lower an error. */
+int64_t kd6d_bop_errors_workspace_floats(int n_problems, int max_scnt);
+int kd6d_bop_errors(int n_problems, const float* verts, const int32_t* voff, const int32_t* vcnt, const float* syms,
+                    const int32_t* soff, const int32_t* scnt, const float* K, const float* Rg, const float* Tg,
+                    const float* Rp, const float* Tp, float* workspace, int64_t workspace_floats, float* err,
+                    void* stream);
 int kd6d_ssc_assign(const kd6d_levels* levels, const float* mask, int mask_h, int mask_w, const float* kp3d,
                     const float* K, const int32_t* class_ids, const int32_t* n_gt, const float* rot,
                     const float* trans, const float* bbox_trans, const float* keys, float positive_num,

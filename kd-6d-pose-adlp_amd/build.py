@@ -39,7 +39,9 @@ EXTRA_FLAGS = {"sinkhorn_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # pnp.hip: the teacher PnP gate runs on the teacher's stream, beside the student's convolutions
                "pnp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # pose_err.hip: a non-MFMA unit like the ones above, same switch (validation runs between training steps)
-               "pose_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "pose_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # bop_err.hip: the second scorer of validation, same kind of unit, same switch
+               "bop_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

@@ -156,6 +156,8 @@ SIGNATURES = {
     "kd6d_teacher_pnp_gate": [_P, _I, _F, _P, _P, _P, _I, _I, _P, _I, _P, _F, _I, ctypes.c_uint64, _P, _I64, _P],
     "kd6d_pose_remap": [_I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_double), _P, _P, _P, _P, _P],
     "kd6d_pose_errors": [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "kd6d_bop_errors_workspace_floats": [_I, _I],
+    "kd6d_bop_errors": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
     "kd6d_ssc_assign": [_L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P],
     "kd6d_focal_fwd": [_P, _P, _I, _F, _F, _P, _P, _P],
     "kd6d_focal_bwd": [_I, _P, _P, _I, _F, _F, _P, _P, _P],

@@ -37,8 +37,8 @@ def custom_cfg(cfg):
 def get_argparser():
     """The reference's options of arguments/argument.py:6-22 that evaluation reads, under their names and defaults, plus
     the additive ones of this build (--synthetic, --precision, --pnp_solver, --eval_scorer, --image_size, --frame_cache,
-    --frame_cache_gb)."""
-    from .argument_kd import add_frame_cache_flags
+    --frame_cache_gb, --bop_metrics, --bop_csv)."""
+    from .argument_kd import add_bop_flags, add_frame_cache_flags
     p = argparse.ArgumentParser()
     p.add_argument("--local_rank", type=int, default=0)
     p.add_argument("--config_file", type=str, default="./configs/ape.yaml")
@@ -58,6 +58,10 @@ def get_argparser():
                    help="pose errors of evaluation: host = float64 numpy, one object at a time "
                         "(kd6d/libs/evaluate.py); device = HIP (csrc/pose_err.hip), every object in one launch")
     add_frame_cache_flags(p)
+    add_bop_flags(p)
+    p.add_argument("--bop_csv", type=str, default="",
+                   help="write every kept prediction in the BOP results format (scene_id,im_id,obj_id,score,R,t,time) to "
+                        "this file; with or without --bop_metrics.  Not with --synthetic")
     return p
 
 
@@ -66,12 +70,16 @@ def get_args(argv=None):
     (LOCAL_RANK, CONFIG_FILE, NUM_WORKERS, WEIGHT_FILE, WORKING_DIR, RUNNING_DEVICE) plus this build's keys."""
     from .argument_kd import frame_cache_runtime, load_yaml
     args = get_argparser().parse_args(argv)
+    if args.bop_csv and args.synthetic:
+        from ..libs.bop_metrics import BOP_CSV_SYNTHETIC_ERROR
+        raise SystemExit(BOP_CSV_SYNTHETIC_ERROR)
     fc = frame_cache_runtime(args)
     cfg = load_yaml(args.config_file)
     cfg["RUNTIME"] = dict(LOCAL_RANK=args.local_rank, CONFIG_FILE=args.config_file, NUM_WORKERS=args.num_workers,
                           WEIGHT_FILE=args.weight_file, WORKING_DIR=args.working_dir,
                           RUNNING_DEVICE=args.running_device, PRECISION=args.precision, SYNTHETIC=bool(args.synthetic),
-                          IMAGE_SIZE=int(args.image_size), PNP_SOLVER=args.pnp_solver, EVAL_SCORER=args.eval_scorer, **fc)
+                          IMAGE_SIZE=int(args.image_size), PNP_SOLVER=args.pnp_solver, EVAL_SCORER=args.eval_scorer,
+                          BOP_METRICS=bool(args.bop_metrics), BOP_CSV=args.bop_csv, **fc)
     if len(args.test_file) > 0:
         cfg["DATASETS"]["TEST"] = args.test_file
     cfg["DATASETS"].setdefault("MIXED_CLASSES", False)

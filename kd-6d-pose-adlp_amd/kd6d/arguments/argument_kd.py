@@ -3,7 +3,7 @@
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
---synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap; yaml files may name a `_BASE_` file.
+--synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --bop_metrics; yaml files may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -103,6 +103,7 @@ def get_argparser():
     p.add_argument("--synthetic_instances", type=int, default=1, choices=[1, 2, 3, 4],
                    help="--synthetic: objects of distinct classes per image (masks in vertical strips)")
     add_frame_cache_flags(p)
+    add_bop_flags(p)
     return p
 
 
@@ -121,6 +122,13 @@ def add_frame_cache_flags(p):
     p.add_argument("--frame_cache_gb", type=float, default=64.,
                    help="--frame_cache device: most GiB of frames + masks one cached list may take per process; a list "
                         "that does not fit is refused before anything is allocated (no fall-back to the host loader)")
+
+
+def add_bop_flags(p):
+    """The flag train_kd.py and test.py share (kd6d/libs/bop_metrics.py)."""
+    p.add_argument("--bop_metrics", action="store_true",
+                   help="validation additionally scores EVERY object with BOP's MSSD and MSPD (all vertices, exact symmetry "
+                        "sets, csrc/bop_err.hip) and reports AR_MSSD, AR_MSPD and their mean; BOP's VSD term is not built")
 
 
 def frame_cache_runtime(args):
@@ -168,7 +176,8 @@ def _runtime(args, config_file, weight_file):
                 TEACHER_PNP_GATE=bool(args.teacher_pnp_gate), PNP_SOLVER=getattr(args, "pnp_solver", "host"),
                 EVAL_SCORER=getattr(args, "eval_scorer", "host"),
                 TWO_LAUNCH_NORM_BWD=bool(args.two_launch_norm_bwd), EXCHANGE=args.exchange,
-                RCCL_SINGLE_RANK=bool(getattr(args, "rccl_single_rank", False)))
+                RCCL_SINGLE_RANK=bool(getattr(args, "rccl_single_rank", False)),
+                BOP_METRICS=bool(getattr(args, "bop_metrics", False)))
 
 
 def build_cfgs(args):

@@ -22,17 +22,23 @@ class _Mesh:
 
 
 @torch.no_grad()
-def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host", preds_out=None):
+def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host", preds_out=None, bop=None):
     """meshes: per class id an (n,3) vertex array (or an object with `.vertices`).  -> the 6-tuple of
     evaluate_pose_predictions on rank 0, None elsewhere.
     scorer: "host" scores object by object in float64 numpy (evaluate_pose_predictions); "device" scores every object of
     the run in one kd6d_pose_errors launch (evaluate_pose_predictions_device).  preds_out: a dict that receives the
-    collected {path: {'meta', 'pred'}} entries (what the reference's valid() writes to preds.json)."""
+    collected {path: {'meta', 'pred'}} entries (what the reference's valid() writes to preds.json).
+    bop: a dict (train_kd.py / test.py --bop_metrics), or None.  With a dict valid() ADDITIONALLY keeps every remapped
+    prediction [score, class, R, T] of every image -- scoring needs each object's pose, not only the most confident one
+    of the image -- in a side collection, scores it on rank 0 with kd6d_bop_errors (csrc/bop_err.hip; always the device,
+    whatever `scorer` says) and fills the dict with bop_metrics.bop_tables' MSSD / MSPD recalls and average recalls, plus
+    the side collection itself under "predictions".  It logs BOP/AR_MSSD, BOP/AR_MSPD and BOP/AR.  The AR has two terms:
+    BOP's VSD term is not built.  The return value and preds_out are the same with and without it."""
     if scorer not in SCORERS:
         raise ValueError("valid(): scorer=%r (one of %s)" % (scorer, ", ".join(SCORERS)))
     was_training = model.training
     model.eval()
-    preds = {}
+    preds, every = {}, {}
     for images, targets, meta_infos in loader:
         if hasattr(images, "to"):
             images = images.to(device)
@@ -47,12 +53,24 @@ def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host",
                                           cfg["INPUT"].get("INTERNAL_HEIGHT"), kp3d, m, p)
             best = [list(p[0][:-1])] if len(p) else []
             preds[m["path"]] = {"meta": m, "pred": best}
+            if bop is not None:
+                every[m["path"]] = {"meta": m, "pred": [list(q[:4]) for q in p]}
     model.train(was_training)
     if preds_out is not None:
         preds_out.update(preds)
+    if bop is not None:
+        bop["predictions"] = every
     if get_rank() != 0:
         return None
     ms = [m if hasattr(m, "vertices") else _Mesh(m) for m in meshes]
+    if bop is not None:
+        from . import bop_metrics as B
+        n_cls = cfg["DATASETS"]["N_CLASS"] - 1
+        bop.update(B.evaluate_bop_predictions(every, cfg["DATASETS"]["N_CLASS"], ms, cfg["DATASETS"]["MESH_DIAMETERS"],
+                                              B.dataset_symmetry_sets(cfg["DATASETS"], n_cls), device))
+        if logger is not None:
+            for k in ("AR_MSSD", "AR_MSPD", "AR"):
+                logger.add_scalar("BOP/" + k, bop[k], steps)
     if scorer == "device":
         out = evaluate_pose_predictions_device(preds, cfg["DATASETS"]["N_CLASS"], ms, cfg["DATASETS"]["MESH_DIAMETERS"],
                                                cfg["DATASETS"].get("SYMMETRY_TYPES", {}), device)

@@ -747,6 +747,53 @@ def pose_errors(verts, voff, vcnt, vidx, K, Rg, Tg, Rp, Tp, sym, max_v=None, wan
     return (err, nn) if want_nn else err
 
 
+def bop_errors(verts, voff, vcnt, syms, soff, scnt, K, Rg, Tg, Rp, Tp, validate=True, max_scnt=None):
+    """MSSD / MSPD of P (ground truth, prediction) pairs in one call (csrc/bop_err.hip; the float64 definition is
+    kd6d.libs.bop_metrics.bop_errors_host).  verts (Nv, 3) fp32 vertex pool; syms (Ns, 12) fp32 symmetry pool (R
+    row-major, then t); voff, vcnt, soff, scnt (P,) int32: problem p scores every vertex voff[p] ... voff[p] + vcnt[p] - 1
+    under the symmetries soff[p] ... soff[p] + scnt[p] - 1 (scnt[p] <= 0: the identity alone; vcnt[p] <= 0: err = 0);
+    K, Rg, Rp (P, 3, 3), Tg, Tp (P, 3) fp32.  -> err (P, 2) = (mssd, mspd), a device tensor.
+    validate: check on the device that every vertex and symmetry index stays inside its pool and read the verdict back
+    (ONE synchronisation, which also yields the largest scnt; the kernel cannot know the pools' sizes).  Callers that
+    built the index arrays themselves and replay the call in a captured graph pass False and max_scnt (the largest
+    scnt[p], which sizes the workspace; without it it is read back from scnt)."""
+    P = voff.numel()
+    dev = verts.device
+    assert verts.dtype == torch.float32 and verts.dim() == 2 and verts.shape[1] == 3
+    assert syms.dtype == torch.float32 and syms.numel() % 12 == 0
+    for t in (voff, vcnt, soff, scnt):
+        assert t.dtype == torch.int32 and t.numel() == P
+    for t, n in ((K, 9), (Rg, 9), (Rp, 9), (Tg, 3), (Tp, 3)):
+        assert t.dtype == torch.float32 and t.numel() == P * n
+    err = torch.empty(P, 2, dtype=torch.float32, device=dev)
+    if P == 0:
+        return err
+    if validate:
+        Nv, Ns = verts.shape[0], syms.numel() // 12
+        vc, sc = vcnt.long().clamp(min=0), scnt.long().clamp(min=0)
+        bad_v = (vc > 0) & ((voff < 0) | (voff.long() + vc > Nv))
+        bad_s = (sc > 0) & ((soff < 0) | (soff.long() + sc > Ns))
+        verdict = torch.stack([bad_v.any().long(), bad_s.any().long(), sc.max()]).tolist()     # the one synchronisation
+        if verdict[0]:
+            raise ValueError("bop_errors: problem %d points outside the vertex pool of %d vertices"
+                             % (int(torch.nonzero(bad_v)[0]), Nv))
+        if verdict[1]:
+            raise ValueError("bop_errors: problem %d points outside the symmetry pool of %d transforms"
+                             % (int(torch.nonzero(bad_s)[0]), Ns))
+        assert max_scnt is None or max_scnt >= verdict[2], "bop_errors: max_scnt=%d < largest scnt %d" % (max_scnt, verdict[2])
+        max_scnt = verdict[2] if max_scnt is None else max_scnt
+    elif max_scnt is None:
+        max_scnt = int(scnt.max())
+    if syms.numel() == 0:             # every problem is identity only: the pool is never read, but the ABI takes no NULL
+        syms = torch.zeros(1, 12, dtype=torch.float32, device=dev)
+    nws = int(lib.kd6d_bop_errors_workspace_floats(P, int(max_scnt)))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    check(lib.kd6d_bop_errors(P, _ptr(verts), _ptr(voff), _ptr(vcnt), _ptr(syms), _ptr(soff), _ptr(scnt), _ptr(K),
+                              _ptr(Rg), _ptr(Tg), _ptr(Rp), _ptr(Tp), _ptr(ws), nws, _ptr(err), _stream()),
+          "kd6d_bop_errors")
+    return err
+
+
 def sinkhorn_dense(x, alpha, y, beta, blur=0.05, scaling=0.5, reach=0.5, diameter=None, p=2.0):
     """Debiased (unbalanced) Sinkhorn divergence between two LARGE weighted point sets: x (N,D), alpha (N),
     y (M,D), beta (M), D in {2,4,8,16} -- losses/kd_loss.py:26-30 / loss_libs.py:47 with a dense grid of local

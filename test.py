@@ -3,7 +3,7 @@ checkpoint without starting a training run.
 
     python test.py --config_file ./configs/ape.yaml --backbone darknet_tiny_h --weight_file outputs/ape/kd/final.pth \
         --working_dir outputs/ape/test/ --pnp_solver device --eval_scorer device [--test_file list.txt | --synthetic]
-        [--frame_cache device]
+        [--frame_cache device] [--bop_metrics] [--bop_csv results.csv]
 
 Builds the network named by --backbone, loads --weight_file (a bare state dict or one under a 'model' key, loosely by
 name as the reference does; says whether weights were loaded or are random), builds the valid-style loader over
@@ -14,6 +14,13 @@ kd6d.libs.eval_libs.valid().  Writes, under --working_dir,
     metrics.json  the six values valid() returns: per-class ADI / AUC / REP accuracies, ADI / REP per depth bin and
                   the depth range
 and prints the per-class ADI / AUC / REP table (utils.py:620-653).
+
+--bop_metrics additionally scores EVERY object (not only the most confident one of an image) with BOP's MSSD and MSPD on
+the device (csrc/bop_err.hip: all vertices, the exact symmetry sets of models_info.json or DATASETS.SYMMETRY_TYPES), adds
+the recalls and average recalls as "bop" to metrics.json and prints one line per class.  The AR it prints is the mean of
+AR_MSSD and AR_MSPD: BOP's third term, VSD, needs depth images and a renderer and is not built.  --bop_csv FILE (with or
+without --bop_metrics, not with --synthetic) writes every kept prediction in the BOP results format
+scene_id,im_id,obj_id,score,R,t,time for the official toolkit.
 
 One process: rank 0 evaluates, as valid() does; the reference's multi-process gather of predictions
 (libs/train_libs.py accumulate_dicts) is not rebuilt.
@@ -84,14 +91,30 @@ def main(argv=None):
         meshes = dataset_meshes(loader)
 
     preds = {}
-    out = valid(cfg, 0, loader, model, device, meshes, scorer=cfg["RUNTIME"]["EVAL_SCORER"], preds_out=preds)
+    want_bop, bop_csv = cfg["RUNTIME"].get("BOP_METRICS", False), cfg["RUNTIME"].get("BOP_CSV", "")
+    bop = {} if (want_bop or bop_csv) else None
+    out = valid(cfg, 0, loader, model, device, meshes, scorer=cfg["RUNTIME"]["EVAL_SCORER"], preds_out=preds, bop=bop)
+    every = bop.pop("predictions") if bop is not None else None
     with open(os.path.join(wd, "preds.json"), "w") as f:
         json.dump(_jsonable(preds), f)
     names = ("adi_per_class", "auc_per_class", "rep_per_class", "adi_per_depth", "rep_per_depth", "depth_range")
+    metrics = dict(zip(names, out))
+    if want_bop:
+        metrics["bop"] = bop
     with open(os.path.join(wd, "metrics.json"), "w") as f:
-        json.dump(_jsonable(dict(zip(names, out))), f, indent=1)
+        json.dump(_jsonable(metrics), f, indent=1)
     print("%d images scored (%s scorer, %s PnP)" % (len(preds), cfg["RUNTIME"]["EVAL_SCORER"], cfg["RUNTIME"]["PNP_SOLVER"]))
     print_accuracy_per_class(out[0], out[1], out[2])
+    if want_bop:
+        from kd6d.libs.bop_metrics import format_ar_line
+        for c, e in enumerate(bop["per_class"]):
+            if e:
+                print("bop cls_%02d\tn %d\tAR_MSSD %.4f\tAR_MSPD %.4f" % (c, e["n"], e["AR_MSSD"], e["AR_MSPD"]))
+        print(format_ar_line(bop))
+    if bop_csv:
+        from kd6d.libs.bop_metrics import class_object_ids, write_bop_csv
+        n = write_bop_csv(bop_csv, every, class_object_ids(cfg["DATASETS"]["MESH_DIR"]))
+        print("%d estimates written to %s (BOP results format)" % (n, bop_csv))
 
 
 if __name__ == "__main__":

@@ -13,7 +13,8 @@ INTERNAL_K included, on the GPU front-end; --frame_cache device decodes every fr
 memory, kd6d/libs/frame_cache.py); with it, seeded LINEMOD-shaped batches.  As in the
 reference the teacher is validated once before training (skip with --skip_teacher_eval) and every VAL_FREQ steps
 rank 0 validates the student (kd6d/libs/eval_libs.valid: eval forward -> pose candidates -> PnP-RANSAC -> ADI /
-REP; --eval_scorer device scores the poses in one launch) and writes latest.pth; test.py scores a saved checkpoint.
+REP; --eval_scorer device scores the poses in one launch; --bop_metrics adds BOP's MSSD / MSPD average recalls of every
+object, csrc/bop_err.hip) and writes latest.pth; test.py scores a saved checkpoint.
 Scalars go to tensorboardX under the reference's tags when that package is installed, else to <working_dir>/scalars.jsonl with the same tags.
 """
 import json
@@ -233,8 +234,12 @@ if __name__ == "__main__":
     for idx, (images, targets, _) in enumerate(train_loader):
         if total_steps >= MAX_ITER:
             if get_rank() == 0:
+                bop = {} if cfg["RUNTIME"].get("BOP_METRICS", False) else None
                 valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger,      # train_kd.py:95-99
-                      scorer=scorer)
+                      scorer=scorer, bop=bop)
+                if bop is not None:
+                    from kd6d.libs.bop_metrics import format_ar_line
+                    print("valid @ %d: %s" % (total_steps, format_ar_line(bop)))
                 torch.save(model.state_dict(), os.path.join(wd, "final.pth"))
             print("Training finished")
             break
@@ -285,9 +290,13 @@ if __name__ == "__main__":
             # leave the others waiting in the next gradient all-reduce.
             stop_if_barrier_timeouts(lib.kd6d_barrier_timeouts(), cfg["RUNTIME"]["DISTRIBUTED"])
         if get_rank() == 0 and total_steps % VAL_FREQ == 0:
+            bop = {} if cfg["RUNTIME"].get("BOP_METRICS", False) else None       # --bop_metrics: MSSD / MSPD of every object
             acc = valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger,     # train_kd.py:148-150
-                        scorer=scorer)
+                        scorer=scorer, bop=bop)
             model.train()
+            if bop is not None:
+                from kd6d.libs.bop_metrics import format_ar_line
+                print("valid @ %d: %s" % (total_steps, format_ar_line(bop)))
             seen = [a for a in acc[0] if a]
             print("valid @ %d: %s" % (total_steps, {k: round(float(sum(a[k] for a in seen)) / len(seen), 2) for k in seen[0]}
                                       if seen else "no objects"))
