@@ -618,6 +618,39 @@ int kd6d_bop_errors(int n_problems, const float* verts, const int32_t* voff, con
                     const int32_t* soff, const int32_t* scnt, const float* K, const float* Rg, const float* Tg,
                     const float* Rp, const float* Tp, float* workspace, int64_t workspace_floats, float* err,
                     void* stream);
+/* ---- BOP's VSD on the device (csrc/bop_vsd.hip; added under ABI 11, new symbols only): a depth rasteriser and the
+ * visible-surface-discrepancy counts of n (ground truth, estimate) pairs.  kd6d/libs/bop_metrics.py holds the float64
+ * definitions (render_depth_host, vsd_errors_host) and the rasteriser contract: pixel centres at integer coordinates,
+ * K = [fx s cx; 0 fy cy; 0 0 1], inclusive edges, both windings, a triangle with a vertex at z <= 0 dropped whole (no
+ * near-plane clipping), depth = the triangle's plane along the pixel's ray clamped to its vertex z range, minimum over
+ * the triangles, background 0.
+ * Item i draws the fcnt[i] triangles faces[foff[i] + f] (int32 triples, indices RELATIVE to voff[i], each < vcnt[i]) of
+ * the vertices verts[voff[i] ...]; n_verts / n_faces are the pools' sizes.  An item whose offsets or counts leave a
+ * pool (or, for kd6d_bop_vsd, whose frame index is outside [0, n_img)) is never dereferenced: its map / counts stay 0;
+ * a face with an index outside [0, vcnt[i]) is skipped (kd6d.ops checks all of this with validate=True).
+ * kd6d_render_depth: depth_out (n, H, W) fp32, the z of the camera frame, under (R[i], T[i]), K[i].
+ * kd6d_bop_vsd: depth (n_img, H, W) fp32 in the vertices' unit (0 = missing), frame[p] the image of problem p.  With
+ * dist = depth * |K^-1 (x, y, 1)| per pixel, vis(t, m) = (t > 0 && m > 0 && m - t <= delta) || (t == 0 && m > 0):
+ *   visib_gt = vis(dist_test, dist_gt),  visib_est = vis(dist_test, dist_est) || (visib_gt && dist_est > 0)
+ *   counts[p] = { n_u = |gt or est|, n_inter = |gt and est|,
+ *                 cost_k = #{inter: |dist_gt - dist_est| >= tau[k] * diameter[p]} + n_u - n_inter,  k < n_tau }
+ *   err[p][k] = cost_k / n_u,  1 when n_u == 0                              (BOP19: visib_mode bop19, the step cost)
+ * tau_host: n_tau <= 16 values read on the host at the call.  workspace: kd6d_bop_vsd_workspace_ints(n) int32 (the
+ * regions of interest), for both entry points.  n == 0 returns success without a launch and reads no pointer.
+ * Bitwise property: the z-test is an unsigned-integer minimum in LDS and the counts are integer sums -- no float
+ * atomics, no accumulators.  A map and counts[p] are pure functions of the item's own inputs: two calls agree bit for
+ * bit, an item scores the same alone and inside any batch, under any order of its faces and with a face repeated;
+ * err is one division of two of those integers. */
+int64_t kd6d_bop_vsd_workspace_ints(int n);
+int kd6d_render_depth(int n, const float* verts, int n_verts, const int32_t* faces, int n_faces, const int32_t* voff,
+                      const int32_t* vcnt, const int32_t* foff, const int32_t* fcnt, const float* K, const float* R,
+                      const float* T, int H, int W, int32_t* workspace, int64_t workspace_ints, float* depth_out,
+                      void* stream);
+int kd6d_bop_vsd(int n, const float* verts, int n_verts, const int32_t* faces, int n_faces, const int32_t* voff,
+                 const int32_t* vcnt, const int32_t* foff, const int32_t* fcnt, const float* K, const float* Rg,
+                 const float* Tg, const float* Rp, const float* Tp, const float* diameter, const int32_t* frame,
+                 const float* depth, int n_img, int H, int W, float delta, const float* tau_host, int n_tau,
+                 int32_t* workspace, int64_t workspace_ints, int32_t* counts, float* err, void* stream);
 int kd6d_ssc_assign(const kd6d_levels* levels, const float* mask, int mask_h, int mask_w, const float* kp3d,
                     const float* K, const int32_t* class_ids, const int32_t* n_gt, const float* rot,
                     const float* trans, const float* bbox_trans, const float* keys, float positive_num,

@@ -41,7 +41,9 @@ EXTRA_FLAGS = {"sinkhorn_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # pose_err.hip: a non-MFMA unit like the ones above, same switch (validation runs between training steps)
                "pose_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # bop_err.hip: the second scorer of validation, same kind of unit, same switch
-               "bop_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "bop_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # bop_vsd.hip: the third scorer of validation (depth rasteriser + VSD counts), same kind of unit, same switch
+               "bop_vsd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

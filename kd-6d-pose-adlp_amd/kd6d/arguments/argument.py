@@ -37,7 +37,7 @@ def custom_cfg(cfg):
 def get_argparser():
     """The reference's options of arguments/argument.py:6-22 that evaluation reads, under their names and defaults, plus
     the additive ones of this build (--synthetic, --precision, --pnp_solver, --eval_scorer, --image_size, --frame_cache,
-    --frame_cache_gb, --bop_metrics, --bop_csv)."""
+    --frame_cache_gb, --bop_metrics, --bop_vsd, --bop_csv)."""
     from .argument_kd import add_bop_flags, add_frame_cache_flags
     p = argparse.ArgumentParser()
     p.add_argument("--local_rank", type=int, default=0)
@@ -68,8 +68,10 @@ def get_argparser():
 def get_args(argv=None):
     """-> cfg: the yaml (a `_BASE_` file honoured) with cfg['RUNTIME'] filled as arguments/argument.py:32-38 does
     (LOCAL_RANK, CONFIG_FILE, NUM_WORKERS, WEIGHT_FILE, WORKING_DIR, RUNNING_DEVICE) plus this build's keys."""
-    from .argument_kd import frame_cache_runtime, load_yaml
-    args = get_argparser().parse_args(argv)
+    from .argument_kd import check_bop_flags, frame_cache_runtime, load_yaml
+    parser = get_argparser()
+    args = parser.parse_args(argv)
+    check_bop_flags(parser, args)
     if args.bop_csv and args.synthetic:
         from ..libs.bop_metrics import BOP_CSV_SYNTHETIC_ERROR
         raise SystemExit(BOP_CSV_SYNTHETIC_ERROR)
@@ -79,7 +81,8 @@ def get_args(argv=None):
                           WEIGHT_FILE=args.weight_file, WORKING_DIR=args.working_dir,
                           RUNNING_DEVICE=args.running_device, PRECISION=args.precision, SYNTHETIC=bool(args.synthetic),
                           IMAGE_SIZE=int(args.image_size), PNP_SOLVER=args.pnp_solver, EVAL_SCORER=args.eval_scorer,
-                          BOP_METRICS=bool(args.bop_metrics), BOP_CSV=args.bop_csv, **fc)
+                          BOP_METRICS=bool(args.bop_metrics), BOP_VSD=bool(args.bop_vsd), BOP_CSV=args.bop_csv,
+                          **fc)
     if len(args.test_file) > 0:
         cfg["DATASETS"]["TEST"] = args.test_file
     cfg["DATASETS"].setdefault("MIXED_CLASSES", False)

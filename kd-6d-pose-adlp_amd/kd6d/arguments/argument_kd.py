@@ -3,7 +3,7 @@
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
---synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --bop_metrics; yaml files may name a `_BASE_` file.
+--synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --bop_metrics, --bop_vsd; yaml files may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -125,10 +125,21 @@ def add_frame_cache_flags(p):
 
 
 def add_bop_flags(p):
-    """The flag train_kd.py and test.py share (kd6d/libs/bop_metrics.py)."""
+    """The flags train_kd.py and test.py share (kd6d/libs/bop_metrics.py)."""
     p.add_argument("--bop_metrics", action="store_true",
                    help="validation additionally scores EVERY object with BOP's MSSD and MSPD (all vertices, exact symmetry "
-                        "sets, csrc/bop_err.hip) and reports AR_MSSD, AR_MSPD and their mean; BOP's VSD term is not built")
+                        "sets, csrc/bop_err.hip) and reports AR_MSSD, AR_MSPD and their mean; BOP's VSD term is not in that mean "
+                        "(--bop_vsd adds it)")
+    p.add_argument("--bop_vsd", action="store_true",
+                   help="with --bop_metrics: additionally score BOP's VSD term on the device (csrc/bop_vsd.hip: a depth "
+                        "rasteriser and the bop19 visibility comparison against the scene's depth/ images; --synthetic "
+                        "renders the frame's depth from its ground truth) and report AR_VSD and the three-term AR_BOP")
+
+
+def check_bop_flags(parser, args):
+    """--bop_vsd needs --bop_metrics: AR_BOP is the mean of AR_VSD and the two terms that flag scores."""
+    if getattr(args, "bop_vsd", False) and not getattr(args, "bop_metrics", False):
+        parser.error("--bop_vsd requires --bop_metrics")
 
 
 def frame_cache_runtime(args):
@@ -177,7 +188,7 @@ def _runtime(args, config_file, weight_file):
                 EVAL_SCORER=getattr(args, "eval_scorer", "host"),
                 TWO_LAUNCH_NORM_BWD=bool(args.two_launch_norm_bwd), EXCHANGE=args.exchange,
                 RCCL_SINGLE_RANK=bool(getattr(args, "rccl_single_rank", False)),
-                BOP_METRICS=bool(getattr(args, "bop_metrics", False)))
+                BOP_METRICS=bool(getattr(args, "bop_metrics", False)), BOP_VSD=bool(getattr(args, "bop_vsd", False)))
 
 
 def build_cfgs(args):
@@ -227,5 +238,7 @@ def build_cfgs(args):
 
 
 def get_args(argv=None):
-    args = get_argparser().parse_args(argv)
+    parser = get_argparser()
+    args = parser.parse_args(argv)
+    check_bop_flags(parser, args)
     return build_cfgs(args)

@@ -101,9 +101,85 @@ def load_ply_vertices(path):
         return np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float64)
 
 
+_PLY_CODES = {"char": "i1", "uchar": "u1", "int8": "i1", "uint8": "u1", "short": "<i2", "ushort": "<u2", "int16": "<i2",
+              "uint16": "<u2", "int": "<i4", "uint": "<u4", "int32": "<i4", "uint32": "<u4", "float": "<f4",
+              "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def load_ply_faces(path):
+    """Triangles (m, 3) int32 of a PLY file (ascii or binary_little_endian): the face element's list property
+    `vertex_indices` / `vertex_index`, with any integer count and index types; polygons are fan-triangulated
+    ((i0, i1, i2), (i0, i2, i3), ...).  Vertex properties of any number and type may stand in front, other elements and
+    other scalar face properties are skipped.  A file without faces gives (0, 3)."""
+    with open(path, "rb") as f:
+        fmt, elements = None, []                       # [name, count, [(kind, name, types)]]
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: no end_header" % path)
+            tok = line.decode("ascii", "replace").strip().split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property" and elements:
+                if tok[1] == "list":
+                    elements[-1][2].append(("list", tok[4], (tok[2], tok[3])))
+                else:
+                    elements[-1][2].append(("scalar", tok[2], (tok[1],)))
+            elif tok[0] == "end_header":
+                break
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError("%s: unsupported PLY format %s" % (path, fmt))
+        tris = []
+        for name, count, props in elements:
+            lists = [p for p in props if p[0] == "list"]
+            if name != "face":
+                if lists:
+                    raise ValueError("%s: list property inside the %s element" % (path, name))
+                if fmt == "ascii":
+                    for _ in range(count):
+                        f.readline()
+                else:
+                    f.seek(count * sum(np.dtype(_PLY_CODES[p[2][0]]).itemsize for p in props), 1)
+                continue
+            if not any(p[1] in ("vertex_indices", "vertex_index") for p in lists):
+                raise ValueError("%s: the face element has no vertex_indices list" % path)
+            for _ in range(count):
+                poly = None
+                if fmt == "ascii":
+                    tok, at = f.readline().split(), 0
+                    for kind, pname, types in props:
+                        if kind == "list":
+                            k = int(tok[at])
+                            vals = [int(t) for t in tok[at + 1:at + 1 + k]]
+                            at += 1 + k
+                            if pname in ("vertex_indices", "vertex_index"):
+                                poly = vals
+                        else:
+                            at += 1
+                else:
+                    for kind, pname, types in props:
+                        if kind == "list":
+                            ct, it = np.dtype(_PLY_CODES[types[0]]), np.dtype(_PLY_CODES[types[1]])
+                            k = int(np.frombuffer(f.read(ct.itemsize), ct, 1)[0])
+                            vals = np.frombuffer(f.read(k * it.itemsize), it, k)
+                            if pname in ("vertex_indices", "vertex_index"):
+                                poly = [int(x) for x in vals]
+                        else:
+                            f.seek(np.dtype(_PLY_CODES[types[0]]).itemsize, 1)
+                for j in range(1, len(poly) - 1):
+                    tris.append((poly[0], poly[j], poly[j + 1]))
+            break
+    return np.asarray(tris, np.int32).reshape(-1, 3)
+
+
 class Mesh:
-    def __init__(self, vertices):
+    def __init__(self, vertices, faces=None):
         self.vertices = vertices
+        self.faces = faces                     # (m, 3) int32 triangles, or None: a vertex-only mesh
 
 
 def load_bop_meshes(model_path):
@@ -112,8 +188,28 @@ def load_bop_meshes(model_path):
     meshes, table = [], {}
     for i, name in enumerate(files):
         table[str(int(os.path.splitext(name)[0][4:]))] = i
-        meshes.append(Mesh(load_ply_vertices(os.path.join(model_path, name))))
+        meshes.append(Mesh(load_ply_vertices(os.path.join(model_path, name)), load_ply_faces(os.path.join(model_path, name))))
     return meshes, table
+
+
+def load_depth_mm(rgb_path, mem_cache=None):
+    """The depth image of a BOP frame in millimetres, (H, W) float32, 0 = missing: '<scene>/rgb/<im>.<ext>' ->
+    '<scene>/depth/<im>.png' (16-bit) times scene_camera.json's depth_scale of that image (1.0 when absent)."""
+    rgb_path = rgb_path.strip()
+    gt_dir, sub, name = rgb_path.rsplit("/", 2)
+    assert sub == "rgb", "BOP layout: <scene>/rgb/<image>"
+    base, _ = os.path.splitext(name)
+    path = gt_dir + "/depth/" + base + ".png"
+    if not os.path.isfile(path):
+        raise FileNotFoundError("depth image %s of frame %s is missing (VSD needs the scene's depth/ directory)"
+                                % (path, rgb_path))
+    raw = load_image_cached(path, None)
+    if raw is None or raw.ndim != 2:
+        raise ValueError("depth image %s: a single-channel 16-bit PNG expected" % path)
+    cam = load_json_cached(gt_dir + "/scene_camera.json", mem_cache)
+    key = str(int(base))
+    cam_a = cam[key] if key in cam else cam[base]
+    return raw.astype(np.float32) * np.float32(cam_a.get("depth_scale", 1.0))
 
 
 def load_bbox_3d(json_file):

@@ -22,7 +22,7 @@ class _Mesh:
 
 
 @torch.no_grad()
-def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host", preds_out=None, bop=None):
+def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host", preds_out=None, vsd=None, bop=None):
     """meshes: per class id an (n,3) vertex array (or an object with `.vertices`).  -> the 6-tuple of
     evaluate_pose_predictions on rank 0, None elsewhere.
     scorer: "host" scores object by object in float64 numpy (evaluate_pose_predictions); "device" scores every object of
@@ -33,7 +33,16 @@ def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host",
     of the image -- in a side collection, scores it on rank 0 with kd6d_bop_errors (csrc/bop_err.hip; always the device,
     whatever `scorer` says) and fills the dict with bop_metrics.bop_tables' MSSD / MSPD recalls and average recalls, plus
     the side collection itself under "predictions".  It logs BOP/AR_MSSD, BOP/AR_MSPD and BOP/AR.  The AR has two terms:
-    BOP's VSD term is not built.  The return value and preds_out are the same with and without it."""
+    BOP's VSD term is not in it.  The return value and preds_out are the same with and without it.
+    vsd: a depth provider (train_kd.py / test.py --bop_vsd), or None; needs `bop`.  depth_fn(meta) -> the frame's (H, W)
+    depth image in mm, 0 = missing (dataset.load_depth_mm of meta["path"], or bop_metrics.rendered_depth_provider for
+    the synthetic loaders); the meshes then carry `.faces`.  valid() scores BOP's VSD of every object on the device
+    (csrc/bop_vsd.hip, bop_metrics.evaluate_bop_vsd) and ADDS to the dict: vsd_thresholds, AR_VSD per class and over
+    the run, AR_BOP = (AR_VSD + AR_MSSD + AR_MSPD) / 3 and AR_BOP_note; it logs BOP/AR_VSD and BOP/AR_BOP.  The existing
+    keys are untouched: "AR" stays the two-term mean with its note.  (Both are passed by keyword; `bop` stays the last
+    parameter of the signature.)"""
+    if vsd is not None and bop is None:
+        raise ValueError("valid(): vsd needs bop={} (AR_BOP is the mean of AR_VSD, AR_MSSD and AR_MSPD)")
     if scorer not in SCORERS:
         raise ValueError("valid(): scorer=%r (one of %s)" % (scorer, ", ".join(SCORERS)))
     was_training = model.training
@@ -71,6 +80,12 @@ def valid(cfg, steps, loader, model, device, meshes, logger=None, scorer="host",
         if logger is not None:
             for k in ("AR_MSSD", "AR_MSPD", "AR"):
                 logger.add_scalar("BOP/" + k, bop[k], steps)
+        if vsd is not None:
+            B.add_vsd_tables(bop, B.evaluate_bop_vsd(every, cfg["DATASETS"]["N_CLASS"], ms,
+                                                     cfg["DATASETS"]["MESH_DIAMETERS"], vsd, device))
+            if logger is not None:
+                for k in ("AR_VSD", "AR_BOP"):
+                    logger.add_scalar("BOP/" + k, bop[k], steps)
     if scorer == "device":
         out = evaluate_pose_predictions_device(preds, cfg["DATASETS"]["N_CLASS"], ms, cfg["DATASETS"]["MESH_DIAMETERS"],
                                                cfg["DATASETS"].get("SYMMETRY_TYPES", {}), device)

@@ -356,6 +356,25 @@ def dataset_meshes(loader):
     return [m.vertices for m in dset.meshes]
 
 
+def vsd_setup(cfg, loader, meshes, device):
+    """--bop_vsd: -> (meshes WITH faces, depth provider) for valid(..., vsd=).  Real data: the dataset's meshes as
+    load_bop_meshes read them and dataset.load_depth_mm of the frame's path.  --synthetic: the surrogate meshes (the 8
+    cube corners) get the cube's 12 triangles, and a frame's depth is the render of all its ground-truth objects (there
+    are no depth images) at INPUT.INTERNAL_WIDTH x INTERNAL_HEIGHT: the synthetic poses and the K of their metas belong
+    to that frame, not to the crop the network sees -- at the crop's size most objects would lie outside the image."""
+    from .dataset import Mesh, load_depth_mm
+    if cfg["RUNTIME"]["SYNTHETIC"]:
+        from ..synthetic import CUBE_FACES
+        from .bop_metrics import rendered_depth_provider
+        ms = [Mesh(m, CUBE_FACES) for m in meshes]
+        return ms, rendered_depth_provider(ms, device, int(cfg["INPUT"].get("INTERNAL_HEIGHT", 480)),
+                                           int(cfg["INPUT"].get("INTERNAL_WIDTH", 640)))
+    dset = loader.loader.dataset
+    dset = dset.datasets[0] if hasattr(dset, "datasets") else dset
+    cache = {}
+    return list(dset.meshes), lambda meta: load_depth_mm(meta["path"], cache)
+
+
 def start_exchange_after_graphs(gstep, model_t, model, first_batch, log=print):
     """Data-parallel run in the grouped launch mode (train_kd.py --launch pipeline --teacher_group > 1, `between` exchange):
     the step's hipGraphs are recorded BEFORE the process's first RCCL communicator exists (graphs instantiated after

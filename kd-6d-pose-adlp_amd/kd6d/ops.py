@@ -794,6 +794,127 @@ def bop_errors(verts, voff, vcnt, syms, soff, scnt, K, Rg, Tg, Rp, Tp, validate=
     return err
 
 
+VSD_MAX_TAU = 16                     # taus one kd6d_bop_vsd call takes
+
+
+def _mesh_items_check(verts, faces, voff, vcnt, foff, fcnt):
+    """The device-side index check of render_depth / bop_vsd -> (items that leave a pool, items with a face index
+    outside [0, vcnt)) as bool tensors; no synchronisation here.  A face index is relative to its item's voff, so the
+    bound depends on the item: the largest and smallest index of a face range come from a sparse table (range
+    maximum in log2(Nf) levels), every item at once."""
+    Nv, Nf = verts.shape[0], faces.shape[0]
+    vc, fc = vcnt.long(), fcnt.long()
+    bad = (voff < 0) | (vc < 1) | (voff.long() + vc > Nv) | (foff < 0) | (fc < 1) | (foff.long() + fc > Nf)
+    if Nf == 0:
+        return bad, torch.zeros_like(bad)
+    hi = [faces.max(dim=1).values.long()]
+    lo = [-faces.min(dim=1).values.long()]
+    while 2 << (len(hi) - 1) <= Nf:
+        h = 1 << (len(hi) - 1)
+        hi.append(torch.maximum(hi[-1][:-h], hi[-1][h:]))
+        lo.append(torch.maximum(lo[-1][:-h], lo[-1][h:]))
+    start = torch.where(bad, torch.zeros_like(fc), foff.long())
+    length = torch.where(bad, torch.ones_like(fc), fc)
+    level = torch.floor(torch.log2(length.double())).long()
+    level = torch.where((2 ** (level + 1)) <= length, level + 1, level)       # guard the rounding of log2
+    level = torch.where((2 ** level) > length, level - 1, level)
+    top, low = torch.zeros_like(fc), torch.zeros_like(fc)
+    for k in range(len(hi)):
+        at = level == k
+        i0 = torch.where(at, start, torch.zeros_like(start)).clamp(max=hi[k].numel() - 1)
+        i1 = torch.where(at, start + length - (1 << k), torch.zeros_like(start)).clamp(0, hi[k].numel() - 1)
+        top = torch.where(at, torch.maximum(hi[k][i0], hi[k][i1]), top)
+        low = torch.where(at, torch.maximum(lo[k][i0], lo[k][i1]), low)
+    return bad, ~bad & ((top >= vc) | (low > 0))
+
+
+def _mesh_items_assert(who, verts, faces, voff, vcnt, foff, fcnt, n):
+    assert verts.dtype == torch.float32 and verts.dim() == 2 and verts.shape[1] == 3
+    assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+    for t in (voff, vcnt, foff, fcnt):
+        assert t.dtype == torch.int32 and t.numel() == n, "%s: four int32 arrays of %d items" % (who, n)
+
+
+def render_depth(verts, faces, voff, vcnt, foff, fcnt, K, R, T, height, width, validate=True):
+    """Depth maps of n (mesh, pose, camera) triples in one call (csrc/bop_vsd.hip; the float64 definition and the
+    rasteriser contract are kd6d.libs.bop_metrics.render_depth_host).  verts (Nv, 3) fp32 vertex pool, faces (Nf, 3)
+    int32 face pool whose indices are relative to the item's voff; voff, vcnt, foff, fcnt (n,) int32; K, R (n, 3, 3),
+    T (n, 3) fp32.  -> (n, height, width) fp32: the camera-frame z of the nearest surface, 0 = background.
+    validate: check on the device that every offset, count and face index stays inside its pool and read the verdict
+    back (ONE synchronisation); nothing is launched when it fails."""
+    n = voff.numel()
+    dev = verts.device
+    _mesh_items_assert("render_depth", verts, faces, voff, vcnt, foff, fcnt, n)
+    for t, k in ((K, 9), (R, 9), (T, 3)):
+        assert t.dtype == torch.float32 and t.numel() == n * k
+    out = torch.empty(n, int(height), int(width), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    if validate:
+        bad, bad_face = _mesh_items_check(verts, faces, voff, vcnt, foff, fcnt)
+        verdict = torch.stack([bad.any(), bad_face.any()]).tolist()                    # the one synchronisation
+        if verdict[0]:
+            raise ValueError("render_depth: item %d points outside the pools of %d vertices and %d faces"
+                             % (int(torch.nonzero(bad)[0]), verts.shape[0], faces.shape[0]))
+        if verdict[1]:
+            raise ValueError("render_depth: item %d has a face index outside its vcnt vertices"
+                             % int(torch.nonzero(bad_face)[0]))
+    nws = int(lib.kd6d_bop_vsd_workspace_ints(n))
+    ws = torch.empty(nws, dtype=torch.int32, device=dev)
+    check(lib.kd6d_render_depth(n, _ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], _ptr(voff), _ptr(vcnt),
+                                _ptr(foff), _ptr(fcnt), _ptr(K), _ptr(R), _ptr(T), int(height), int(width), _ptr(ws),
+                                nws, _ptr(out), _stream()), "kd6d_render_depth")
+    return out
+
+
+def bop_vsd(verts, faces, voff, vcnt, foff, fcnt, K, Rg, Tg, Rp, Tp, diameter, frame, depth, delta, taus,
+            validate=True):
+    """BOP's VSD of P (ground truth, estimate) pairs in one call (csrc/bop_vsd.hip; the float64 definition is
+    kd6d.libs.bop_metrics.vsd_errors_host).  Pools and index arrays as render_depth; K, Rg, Rp (P, 3, 3), Tg, Tp
+    (P, 3), diameter (P,) fp32; frame (P,) int32 = the problem's image in depth (n_img, H, W) fp32 (the vertices' unit,
+    0 = missing); delta: the visibility tolerance; taus: up to 16 floats (a host sequence).
+    -> counts (P, 2 + n_tau) int32 = (n_u, n_inter, cost_k ...), err (P, n_tau) fp32 = cost_k / n_u (1 when n_u == 0):
+    device tensors.
+    validate: check on the device that every offset, count, face index and frame index stays inside its pool and read
+    the verdict back (ONE synchronisation); nothing is launched when it fails.  Callers that built the index arrays
+    themselves and replay the call in a captured graph pass False."""
+    P = voff.numel()
+    dev = verts.device
+    taus = [float(t) for t in taus]
+    assert 1 <= len(taus) <= VSD_MAX_TAU, "bop_vsd: %d taus (1 ... %d)" % (len(taus), VSD_MAX_TAU)
+    _mesh_items_assert("bop_vsd", verts, faces, voff, vcnt, foff, fcnt, P)
+    for t, k in ((K, 9), (Rg, 9), (Rp, 9), (Tg, 3), (Tp, 3), (diameter, 1)):
+        assert t.dtype == torch.float32 and t.numel() == P * k
+    assert frame.dtype == torch.int32 and frame.numel() == P
+    assert depth.dtype == torch.float32 and depth.dim() == 3
+    n_img, H, W = depth.shape
+    counts = torch.empty(P, 2 + len(taus), dtype=torch.int32, device=dev)
+    err = torch.empty(P, len(taus), dtype=torch.float32, device=dev)
+    if P == 0:
+        return counts, err
+    if validate:
+        bad, bad_face = _mesh_items_check(verts, faces, voff, vcnt, foff, fcnt)
+        bad_frame = (frame < 0) | (frame >= n_img)
+        verdict = torch.stack([bad.any(), bad_face.any(), bad_frame.any()]).tolist()   # the one synchronisation
+        if verdict[0]:
+            raise ValueError("bop_vsd: problem %d points outside the pools of %d vertices and %d faces"
+                             % (int(torch.nonzero(bad)[0]), verts.shape[0], faces.shape[0]))
+        if verdict[1]:
+            raise ValueError("bop_vsd: problem %d has a face index outside its vcnt vertices"
+                             % int(torch.nonzero(bad_face)[0]))
+        if verdict[2]:
+            raise ValueError("bop_vsd: problem %d points outside the depth pool of %d images"
+                             % (int(torch.nonzero(bad_frame)[0]), n_img))
+    nws = int(lib.kd6d_bop_vsd_workspace_ints(P))
+    ws = torch.empty(nws, dtype=torch.int32, device=dev)
+    tau_c = (ctypes.c_float * len(taus))(*taus)
+    check(lib.kd6d_bop_vsd(P, _ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], _ptr(voff), _ptr(vcnt),
+                           _ptr(foff), _ptr(fcnt), _ptr(K), _ptr(Rg), _ptr(Tg), _ptr(Rp), _ptr(Tp), _ptr(diameter),
+                           _ptr(frame), _ptr(depth), int(n_img), int(H), int(W), float(delta), tau_c, len(taus),
+                           _ptr(ws), nws, _ptr(counts), _ptr(err), _stream()), "kd6d_bop_vsd")
+    return counts, err
+
+
 def sinkhorn_dense(x, alpha, y, beta, blur=0.05, scaling=0.5, reach=0.5, diameter=None, p=2.0):
     """Debiased (unbalanced) Sinkhorn divergence between two LARGE weighted point sets: x (N,D), alpha (N),
     y (M,D), beta (M), D in {2,4,8,16} -- losses/kd_loss.py:26-30 / loss_libs.py:47 with a dense grid of local

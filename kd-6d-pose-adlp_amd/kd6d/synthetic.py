@@ -24,6 +24,11 @@ def cube_keypoints(diameters=MESH_DIAMETERS):
     return signs[None] * e[:, None, None]
 
 
+# the 12 triangles of cube_keypoints' corners (corner index 4 ix + 2 iy + iz): what --bop_vsd renders for a surrogate mesh
+CUBE_FACES = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6],
+                       [0, 6, 4], [1, 5, 7], [1, 7, 3]], np.int32)
+
+
 def _random_rotation(rng):
     q, r = np.linalg.qr(rng.standard_normal((3, 3)))
     q = q * np.sign(np.diag(r))[None, :]

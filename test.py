@@ -3,7 +3,7 @@ checkpoint without starting a training run.
 
     python test.py --config_file ./configs/ape.yaml --backbone darknet_tiny_h --weight_file outputs/ape/kd/final.pth \
         --working_dir outputs/ape/test/ --pnp_solver device --eval_scorer device [--test_file list.txt | --synthetic]
-        [--frame_cache device] [--bop_metrics] [--bop_csv results.csv]
+        [--frame_cache device] [--bop_metrics [--bop_vsd]] [--bop_csv results.csv]
 
 Builds the network named by --backbone, loads --weight_file (a bare state dict or one under a 'model' key, loosely by
 name as the reference does; says whether weights were loaded or are random), builds the valid-style loader over
@@ -18,8 +18,11 @@ and prints the per-class ADI / AUC / REP table (utils.py:620-653).
 --bop_metrics additionally scores EVERY object (not only the most confident one of an image) with BOP's MSSD and MSPD on
 the device (csrc/bop_err.hip: all vertices, the exact symmetry sets of models_info.json or DATASETS.SYMMETRY_TYPES), adds
 the recalls and average recalls as "bop" to metrics.json and prints one line per class.  The AR it prints is the mean of
-AR_MSSD and AR_MSPD: BOP's third term, VSD, needs depth images and a renderer and is not built.  --bop_csv FILE (with or
-without --bop_metrics, not with --synthetic) writes every kept prediction in the BOP results format
+AR_MSSD and AR_MSPD: BOP's third term, VSD, needs depth images and a renderer and is not in it.  --bop_vsd (with
+--bop_metrics) scores that term too, on the device (csrc/bop_vsd.hip: a depth rasteriser and the bop19 visibility comparison
+against <scene>/depth/<im>.png; --synthetic renders a frame's depth from its ground truth), adds AR_VSD and the three-term
+AR_BOP = (AR_VSD + AR_MSSD + AR_MSPD) / 3 to the "bop" block and prints a three-term line instead of the two-term one.
+--bop_csv FILE (with or without --bop_metrics, not with --synthetic) writes every kept prediction in the BOP results format
 scene_id,im_id,obj_id,score,R,t,time for the official toolkit.
 
 One process: rank 0 evaluates, as valid() does; the reference's multi-process gather of predictions
@@ -93,7 +96,12 @@ def main(argv=None):
     preds = {}
     want_bop, bop_csv = cfg["RUNTIME"].get("BOP_METRICS", False), cfg["RUNTIME"].get("BOP_CSV", "")
     bop = {} if (want_bop or bop_csv) else None
-    out = valid(cfg, 0, loader, model, device, meshes, scorer=cfg["RUNTIME"]["EVAL_SCORER"], preds_out=preds, bop=bop)
+    vsd = None
+    if cfg["RUNTIME"].get("BOP_VSD", False):
+        from kd6d.libs.train_libs import vsd_setup
+        meshes, vsd = vsd_setup(cfg, loader, meshes, device)
+    out = valid(cfg, 0, loader, model, device, meshes, scorer=cfg["RUNTIME"]["EVAL_SCORER"], preds_out=preds, bop=bop,
+                **({"vsd": vsd} if vsd is not None else {}))
     every = bop.pop("predictions") if bop is not None else None
     with open(os.path.join(wd, "preds.json"), "w") as f:
         json.dump(_jsonable(preds), f)
@@ -106,11 +114,14 @@ def main(argv=None):
     print("%d images scored (%s scorer, %s PnP)" % (len(preds), cfg["RUNTIME"]["EVAL_SCORER"], cfg["RUNTIME"]["PNP_SOLVER"]))
     print_accuracy_per_class(out[0], out[1], out[2])
     if want_bop:
-        from kd6d.libs.bop_metrics import format_ar_line
+        from kd6d.libs.bop_metrics import format_ar_bop_line, format_ar_line
         for c, e in enumerate(bop["per_class"]):
-            if e:
+            if e and vsd is not None:
+                print("bop cls_%02d\tn %d\tAR_VSD %.4f\tAR_MSSD %.4f\tAR_MSPD %.4f"
+                      % (c, e["n"], e["AR_VSD"], e["AR_MSSD"], e["AR_MSPD"]))
+            elif e:
                 print("bop cls_%02d\tn %d\tAR_MSSD %.4f\tAR_MSPD %.4f" % (c, e["n"], e["AR_MSSD"], e["AR_MSPD"]))
-        print(format_ar_line(bop))
+        print(format_ar_bop_line(bop) if vsd is not None else format_ar_line(bop))
     if bop_csv:
         from kd6d.libs.bop_metrics import class_object_ids, write_bop_csv
         n = write_bop_csv(bop_csv, every, class_object_ids(cfg["DATASETS"]["MESH_DIR"]))

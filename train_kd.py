@@ -14,7 +14,7 @@ memory, kd6d/libs/frame_cache.py); with it, seeded LINEMOD-shaped batches.  As i
 reference the teacher is validated once before training (skip with --skip_teacher_eval) and every VAL_FREQ steps
 rank 0 validates the student (kd6d/libs/eval_libs.valid: eval forward -> pose candidates -> PnP-RANSAC -> ADI /
 REP; --eval_scorer device scores the poses in one launch; --bop_metrics adds BOP's MSSD / MSPD average recalls of every
-object, csrc/bop_err.hip) and writes latest.pth; test.py scores a saved checkpoint.
+object, csrc/bop_err.hip, and --bop_vsd with it BOP's VSD term and the three-term AR_BOP, csrc/bop_vsd.hip) and writes latest.pth; test.py scores a saved checkpoint.
 Scalars go to tensorboardX under the reference's tags when that package is installed, else to <working_dir>/scalars.jsonl with the same tags.
 """
 import json
@@ -166,6 +166,11 @@ if __name__ == "__main__":
                     yield item
         train_loader = epochs(train_loader)
     cfg["KD"]["vis_dir"] = cfg["RUNTIME"]["WORKING_DIR"]
+    vsd_kw = {}                                                                # --bop_vsd: the student's validations score VSD too
+    if cfg["RUNTIME"].get("BOP_VSD", False) and get_rank() == 0:
+        from kd6d.libs.train_libs import vsd_setup
+        vsd_meshes, vsd_fn = vsd_setup(cfg, valid_loader, valid_meshes, device)
+        vsd_kw = {"vsd": vsd_fn}
 
     print("Building teacher ......")
     model_t = build_model_teacher(cfg_t, PoseModule, device)
@@ -235,11 +240,11 @@ if __name__ == "__main__":
         if total_steps >= MAX_ITER:
             if get_rank() == 0:
                 bop = {} if cfg["RUNTIME"].get("BOP_METRICS", False) else None
-                valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger,      # train_kd.py:95-99
-                      scorer=scorer, bop=bop)
+                valid(cfg, total_steps, valid_loader, model, device, vsd_meshes if vsd_kw else valid_meshes,      # train_kd.py:95-99
+                      logger=logger, scorer=scorer, bop=bop, **vsd_kw)
                 if bop is not None:
-                    from kd6d.libs.bop_metrics import format_ar_line
-                    print("valid @ %d: %s" % (total_steps, format_ar_line(bop)))
+                    from kd6d.libs.bop_metrics import format_ar_bop_line, format_ar_line
+                    print("valid @ %d: %s" % (total_steps, format_ar_bop_line(bop) if vsd_kw else format_ar_line(bop)))
                 torch.save(model.state_dict(), os.path.join(wd, "final.pth"))
             print("Training finished")
             break
@@ -291,12 +296,12 @@ if __name__ == "__main__":
             stop_if_barrier_timeouts(lib.kd6d_barrier_timeouts(), cfg["RUNTIME"]["DISTRIBUTED"])
         if get_rank() == 0 and total_steps % VAL_FREQ == 0:
             bop = {} if cfg["RUNTIME"].get("BOP_METRICS", False) else None       # --bop_metrics: MSSD / MSPD of every object
-            acc = valid(cfg, total_steps, valid_loader, model, device, valid_meshes, logger=logger,     # train_kd.py:148-150
-                        scorer=scorer, bop=bop)
+            acc = valid(cfg, total_steps, valid_loader, model, device, vsd_meshes if vsd_kw else valid_meshes,     # train_kd.py:148-150
+                        logger=logger, scorer=scorer, bop=bop, **vsd_kw)
             model.train()
             if bop is not None:
-                from kd6d.libs.bop_metrics import format_ar_line
-                print("valid @ %d: %s" % (total_steps, format_ar_line(bop)))
+                from kd6d.libs.bop_metrics import format_ar_bop_line, format_ar_line
+                print("valid @ %d: %s" % (total_steps, format_ar_bop_line(bop) if vsd_kw else format_ar_line(bop)))
             seen = [a for a in acc[0] if a]
             print("valid @ %d: %s" % (total_steps, {k: round(float(sum(a[k] for a in seen)) / len(seen), 2) for k in seen[0]}
                                       if seen else "no objects"))
