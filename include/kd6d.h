@@ -651,6 +651,41 @@ int kd6d_bop_vsd(int n, const float* verts, int n_verts, const int32_t* faces, i
                  const float* Tg, const float* Rp, const float* Tp, const float* diameter, const int32_t* frame,
                  const float* depth, int n_img, int H, int W, float delta, const float* tau_host, int n_tau,
                  int32_t* workspace, int64_t workspace_ints, int32_t* counts, float* err, void* stream);
+/* ---- training frames on the device (csrc/render_frames.hip; added under ABI 11, new symbols only): a colour rasteriser.
+ * One call draws n_frames frames of H x W pixels; frame f shows the items with item_frame[i] == f, each in its own slot
+ * g = item_slot[i] < KD6D_MAX_GT, over backgrounds[bg_index[f]].  kd6d/libs/render.py::render_frames_host is the float64
+ * definition.  Mesh pools, offsets and counts as kd6d_render_depth (faces relative to voff[i]); vcol: uint8 RGB per vertex,
+ * indexed as verts; R (n_items, 9), T (n_items, 3); per frame K (n_frames, 9), light (n_frames, 3: a unit vector of the
+ * camera frame pointing FROM the surface TO the light), ambient (n_frames) in [0, 1], bg_index (n_frames);
+ * backgrounds (n_bg, H, W, 3) uint8, copied as they are (BGR).
+ * Coverage and depth: the rasteriser contract above, bit for bit (both units share csrc/kd6d_raster.h): the depth of a
+ * frame with one item equals kd6d_render_depth's map of that item.
+ * Owner: the triangle of the smallest depth at the pixel; among triangles of bit-equal depth the lowest (slot, face index).
+ * Colour, from the owner (vertices v0 v1 v2 with colours c0 c1 c2 and camera z Z0 Z1 Z2; E01, E12, E20 the projected edge
+ * functions of the pixel centre times the sign of the projected area, as in the coverage test):
+ *   b0 = E12 / Z0, b1 = E20 / Z1, b2 = E01 / Z2          (perspective-correct barycentric weights, normalised below)
+ *   albedo_c = (b0 c0_c + b1 c1_c + b2 c2_c) / (b0 + b1 + b2)
+ *   n = R normalize((v1 - v0) x (v2 - v0)), negated when n . X0 > 0 so that it faces the camera
+ *   shade = ambient + (1 - ambient) max(0, n . light)
+ *   channel = clamp(floor(albedo_c * shade + 0.5), 0, 255)
+ * Outputs: frames_out (n_frames, H, W, 3) uint8 BGR; masks_out (n_frames, H, W) uint8, 0 = background, g + 1 = the slot
+ * that owns the pixel (the VISIBLE mask); depth_out (n_frames, H, W) fp32 or NULL.  A pixel without an owner takes the
+ * background's pixel (zeros when bg_index[f] is outside [0, n_bg)), mask 0, depth 0.
+ * An item whose offsets or counts leave a pool, whose fcnt >= 2^28, whose frame is outside [0, n_frames) or whose slot is
+ * outside [0, KD6D_MAX_GT) is never dereferenced and draws nothing; of several items that claim one (frame, slot) the one
+ * of the lowest index is drawn; a face with an index outside [0, vcnt[i]) is skipped (kd6d.ops checks all of this with
+ * validate=True).  n_frames == 0 returns success without a launch; n_items == 0 gives the backgrounds.
+ * workspace: kd6d_render_frames_workspace_ints(n_frames, n_items) int32.
+ * Bitwise property: two unsigned-integer minima in LDS (depth bits, then the packed owner id) decide every pixel -- no
+ * float atomics, no global z-buffer.  A frame is a pure function of its own inputs: two calls agree bit for bit, a frame
+ * is the same alone and inside any batch, under any order of the items and with a face repeated. */
+int64_t kd6d_render_frames_workspace_ints(int n_frames, int n_items);
+int kd6d_render_frames(int n_frames, int n_items, const float* verts, int n_verts, const int32_t* faces, int n_faces,
+                       const uint8_t* vcol, const int32_t* voff, const int32_t* vcnt, const int32_t* foff,
+                       const int32_t* fcnt, const int32_t* item_frame, const int32_t* item_slot, const float* R,
+                       const float* T, const float* K, const float* light, const float* ambient,
+                       const int32_t* bg_index, const uint8_t* backgrounds, int n_bg, int H, int W, int32_t* workspace,
+                       int64_t workspace_ints, uint8_t* frames_out, uint8_t* masks_out, float* depth_out, void* stream);
 int kd6d_ssc_assign(const kd6d_levels* levels, const float* mask, int mask_h, int mask_w, const float* kp3d,
                     const float* K, const int32_t* class_ids, const int32_t* n_gt, const float* rot,
                     const float* trans, const float* bbox_trans, const float* keys, float positive_num,

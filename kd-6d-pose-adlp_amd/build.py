@@ -43,7 +43,10 @@ EXTRA_FLAGS = {"sinkhorn_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # bop_err.hip: the second scorer of validation, same kind of unit, same switch
                "bop_err.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # bop_vsd.hip: the third scorer of validation (depth rasteriser + VSD counts), same kind of unit, same switch
-               "bop_vsd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "bop_vsd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # render_frames.hip: the colour rasteriser of the rendered frame source shares bop_vsd.hip's walk
+               # (kd6d_raster.h) and must form the same bits: the same switch
+               "render_frames.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

@@ -162,6 +162,9 @@ SIGNATURES = {
     "kd6d_render_depth": [_I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I64, _P, _P],
     "kd6d_bop_vsd": [_I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F,
                      ctypes.POINTER(ctypes.c_float), _I, _P, _I64, _P, _P, _P],
+    "kd6d_render_frames_workspace_ints": [_I, _I],
+    "kd6d_render_frames": [_I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P,
+                           _I64, _P, _P, _P, _P],
     "kd6d_ssc_assign": [_L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P],
     "kd6d_focal_fwd": [_P, _P, _I, _F, _F, _P, _P, _P],
     "kd6d_focal_bwd": [_I, _P, _P, _I, _F, _F, _P, _P, _P],
@@ -196,7 +199,7 @@ SIGNATURES = {
     "kd6d_comm_destroy": [_P],
 }
 _RESTYPE = {"kd6d_last_error": ctypes.c_char_p, "kd6d_ctx_current": ctypes.c_void_p,
-            "kd6d_bop_vsd_workspace_ints": ctypes.c_int64}
+            "kd6d_bop_vsd_workspace_ints": ctypes.c_int64, "kd6d_render_frames_workspace_ints": ctypes.c_int64}
 
 
 class Kd6dError(RuntimeError):

@@ -37,8 +37,8 @@ def custom_cfg(cfg):
 def get_argparser():
     """The reference's options of arguments/argument.py:6-22 that evaluation reads, under their names and defaults, plus
     the additive ones of this build (--synthetic, --precision, --pnp_solver, --eval_scorer, --image_size, --frame_cache,
-    --frame_cache_gb, --bop_metrics, --bop_vsd, --bop_csv)."""
-    from .argument_kd import add_bop_flags, add_frame_cache_flags
+    --frame_cache_gb, --bop_metrics, --bop_vsd, --bop_csv, --frame_source and the --render_* flags)."""
+    from .argument_kd import add_bop_flags, add_frame_cache_flags, add_render_flags
     p = argparse.ArgumentParser()
     p.add_argument("--local_rank", type=int, default=0)
     p.add_argument("--config_file", type=str, default="./configs/ape.yaml")
@@ -59,6 +59,7 @@ def get_argparser():
                         "(kd6d/libs/evaluate.py); device = HIP (csrc/pose_err.hip), every object in one launch")
     add_frame_cache_flags(p)
     add_bop_flags(p)
+    add_render_flags(p, training=False)
     p.add_argument("--bop_csv", type=str, default="",
                    help="write every kept prediction in the BOP results format (scene_id,im_id,obj_id,score,R,t,time) to "
                         "this file; with or without --bop_metrics.  Not with --synthetic")
@@ -68,7 +69,7 @@ def get_argparser():
 def get_args(argv=None):
     """-> cfg: the yaml (a `_BASE_` file honoured) with cfg['RUNTIME'] filled as arguments/argument.py:32-38 does
     (LOCAL_RANK, CONFIG_FILE, NUM_WORKERS, WEIGHT_FILE, WORKING_DIR, RUNNING_DEVICE) plus this build's keys."""
-    from .argument_kd import check_bop_flags, frame_cache_runtime, load_yaml
+    from .argument_kd import check_bop_flags, frame_cache_runtime, load_yaml, render_runtime
     parser = get_argparser()
     args = parser.parse_args(argv)
     check_bop_flags(parser, args)
@@ -76,6 +77,7 @@ def get_args(argv=None):
         from ..libs.bop_metrics import BOP_CSV_SYNTHETIC_ERROR
         raise SystemExit(BOP_CSV_SYNTHETIC_ERROR)
     fc = frame_cache_runtime(args)
+    fc.update(render_runtime(args))
     cfg = load_yaml(args.config_file)
     cfg["RUNTIME"] = dict(LOCAL_RANK=args.local_rank, CONFIG_FILE=args.config_file, NUM_WORKERS=args.num_workers,
                           WEIGHT_FILE=args.weight_file, WORKING_DIR=args.working_dir,

@@ -3,7 +3,8 @@
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
---synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --bop_metrics, --bop_vsd; yaml files may name a `_BASE_` file.
+--synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --bop_metrics, --bop_vsd, --frame_source and
+the --render_* flags; yaml files may name a `_BASE_` file.
 """
 import argparse
 import os
@@ -104,7 +105,56 @@ def get_argparser():
                    help="--synthetic: objects of distinct classes per image (masks in vertical strips)")
     add_frame_cache_flags(p)
     add_bop_flags(p)
+    add_render_flags(p, training=True)
     return p
+
+
+RENDER_SYNTHETIC_ERROR = ("--frame_source render cannot be combined with --synthetic: both replace the image lists, "
+                          "choose one")
+RENDER_FRAME_CACHE_ERROR = ("--frame_source render cannot be combined with --frame_cache device: rendered frames already "
+                            "live in device memory (--frame_cache_gb bounds them) and there is no image list to cache")
+
+
+def add_render_flags(p, training):
+    """The flags of the rendered frame source (kd6d/libs/render_source.py, csrc/render_frames.hip); both entry points take all of
+    them; test.py renders the valid list alone and does not use the two of the training list."""
+    p.add_argument("--frame_source", type=str, default="list", choices=["list", "render"],
+                   help="list = the image lists of the yaml (or --synthetic); render = frames drawn on the GPU by "
+                        "kd6d_render_frames: shaded objects at random poses over a background, with their visible "
+                        "masks, kept in device memory and fed through the frame cache's loader (DZI crop, --augment and "
+                        "--aug_pose_remap apply unchanged).  Not with --synthetic or --frame_cache device")
+    p.add_argument("--render_meshes", type=str, default="surrogate", choices=["dataset", "surrogate"],
+                   help="dataset = the PLYs of DATASETS.MESH_DIR (faces, per-vertex red/green/blue; grey without) with "
+                        "DATASETS.BBOX_FILE; surrogate = one coloured ellipsoid per class inside the class's cube box, "
+                        "nothing read from disk")
+    p.add_argument("--render_valid_frames", type=int, default=256,
+                   help="frames of the rendered valid / test list (a fixed seed, never refreshed)")
+    p.add_argument("--render_instances", type=int, default=1, choices=[1, 2, 3, 4],
+                   help="a rendered frame shows 1 ... N objects of distinct classes; they may occlude one another")
+    p.add_argument("--render_backgrounds", type=str, default="noise",
+                   help="noise = procedural low-frequency colour fields; or a directory of .png / .jpg files at the "
+                        "frame size (a file of another size is refused)")
+    p.add_argument("--render_seed", type=int, default=0, help="seed of the rendered scenes (mixed with the rank)")
+    only = "" if training else " (test.py renders the valid list alone: accepted, not used)"
+    p.add_argument("--render_frames", type=int, default=2048, help="frames of the rendered training list per rank" + only)
+    p.add_argument("--render_refresh", type=str, default="epoch", choices=["epoch", "never"],
+                   help="epoch = redraw and re-render the training list after every pass, in place" + only)
+
+
+def render_runtime(args):
+    """-> the RUNTIME keys of the rendered frame source; refuses --frame_source render with --synthetic or with
+    --frame_cache device."""
+    source = getattr(args, "frame_source", "list")
+    if source == "render" and bool(getattr(args, "synthetic", False)):
+        raise SystemExit(RENDER_SYNTHETIC_ERROR)
+    if source == "render" and getattr(args, "frame_cache", "off") != "off":
+        raise SystemExit(RENDER_FRAME_CACHE_ERROR)
+    return dict(FRAME_SOURCE=source, RENDER_MESHES=getattr(args, "render_meshes", "surrogate"),
+                RENDER_FRAMES=int(getattr(args, "render_frames", 2048)),
+                RENDER_VALID_FRAMES=int(getattr(args, "render_valid_frames", 256)),
+                RENDER_INSTANCES=int(getattr(args, "render_instances", 1)),
+                RENDER_REFRESH=getattr(args, "render_refresh", "epoch"),
+                RENDER_BACKGROUNDS=getattr(args, "render_backgrounds", "noise"), RENDER_SEED=int(getattr(args, "render_seed", 0)))
 
 
 FRAME_CACHE_SYNTHETIC_ERROR = ("--frame_cache device cannot be combined with --synthetic: synthetic batches are made on the "
@@ -202,6 +252,7 @@ def build_cfgs(args):
     cfg["RUNTIME"]["AUGMENT"] = bool(getattr(args, "augment", False))
     cfg["RUNTIME"]["AUG_POSE_REMAP"] = aug_pose_remap_runtime(args)
     cfg["RUNTIME"].update(frame_cache_runtime(args))
+    cfg["RUNTIME"].update(render_runtime(args))
     cfg["RUNTIME"]["SKIP_TEACHER_EVAL"] = bool(args.skip_teacher_eval)
     cfg["RUNTIME"]["LAUNCH"] = args.launch
     cfg["RUNTIME"]["TEACHER_GROUP"] = max(1, int(args.teacher_group))

@@ -101,6 +101,51 @@ def load_ply_vertices(path):
         return np.stack([data["x"], data["y"], data["z"]], 1).astype(np.float64)
 
 
+def load_ply_colors(path):
+    """Per-vertex colours (n, 3) uint8 RGB of a PLY file (ascii or binary_little_endian): the vertex properties
+    red / green / blue (uchar, or a float type in 0 ... 1); grey 128 for a file that has none (what the renderer of the
+    rendered frame source then shades)."""
+    with open(path, "rb") as f:
+        fmt, n_vert, props, in_vertex = None, 0, [], False
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: no end_header" % path)
+            tok = line.decode("ascii", "replace").strip().split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                if tok[1] != "vertex" and not props:
+                    raise ValueError("%s: the vertex element must come first" % path)
+                in_vertex = tok[1] == "vertex"
+                if in_vertex:
+                    n_vert = int(tok[2])
+            elif tok[0] == "property" and in_vertex:
+                if tok[1] == "list":
+                    raise ValueError("%s: list property inside the vertex element" % path)
+                props.append((tok[2], tok[1]))
+            elif tok[0] == "end_header":
+                break
+        names = [p[0] for p in props]
+        if not all(c in names for c in ("red", "green", "blue")):
+            return np.full((n_vert, 3), 128, np.uint8)
+        if fmt == "ascii":
+            at = [names.index(c) for c in ("red", "green", "blue")]
+            rows = [f.readline().split() for _ in range(n_vert)]
+            data = {c: np.asarray([float(r[i]) for r in rows]) for c, i in zip(("red", "green", "blue"), at)}
+        elif fmt == "binary_little_endian":
+            dt = np.dtype([(name, _PLY_CODES[t]) for name, t in props])
+            data = np.frombuffer(f.read(n_vert * dt.itemsize), dtype=dt, count=n_vert)
+        else:
+            raise ValueError("%s: unsupported PLY format %s" % (path, fmt))
+        types = dict(props)
+        out = np.stack([np.asarray(data[c], np.float64) * (255.0 if types[c] in ("float", "float32", "double", "float64")
+                                                           else 1.0) for c in ("red", "green", "blue")], axis=1)
+        return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+
+
 _PLY_CODES = {"char": "i1", "uchar": "u1", "int8": "i1", "uint8": "u1", "short": "<i2", "ushort": "<u2", "int16": "<i2",
               "uint16": "<u2", "int": "<i4", "uint": "<u4", "int32": "<i4", "uint32": "<u4", "float": "<f4",
               "float32": "<f4", "double": "<f8", "float64": "<f8"}

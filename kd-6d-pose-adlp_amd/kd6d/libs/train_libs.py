@@ -226,11 +226,14 @@ class CachedDziLoader(DziLoader):
     go through the unchanged kd6d_dzi_crop / AugmentFront.  `loader` is the host DataLoader the run would have used; it
     is kept for its length, data set and sampler and never iterated."""
 
-    def __init__(self, loader, cfg, device, training, augment=False, budget_bytes=64 * 2 ** 30, log=print):
-        from .frame_cache import DeviceFrameCache
+    def __init__(self, loader, cfg, device, training, augment=False, budget_bytes=64 * 2 ** 30, log=print, cache=None):
+        """cache: a store with DeviceFrameCache's interface to iterate over instead of building one (RenderedDziLoader)."""
         super().__init__(loader, cfg, device, training, augment=augment)
-        self.cache = DeviceFrameCache(loader.dataset, device, budget_bytes,
-                                      num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0), log=log)
+        if cache is None:
+            from .frame_cache import DeviceFrameCache
+            cache = DeviceFrameCache(loader.dataset, device, budget_bytes,
+                                     num_workers=cfg["RUNTIME"].get("NUM_WORKERS", 0), log=log)
+        self.cache = cache
         H, W = self.cache.H, self.cache.W
         if self.front is None and (H, W) != tuple(self.size):
             raise ValueError("frames are %dx%d but INPUT.INTERNAL_* is %dx%d: the CPU Resize transform of the reference "
@@ -280,6 +283,86 @@ class CachedDziLoader(DziLoader):
             _, frames, masks = c.gather(slots)
             yield self._augment_batch(frames, masks, [c.targets[s] for s in slots], [c.metas[s] for s in slots],
                                       collate_params(params))
+
+
+class RenderedDziLoader(CachedDziLoader):
+    """CachedDziLoader over a store that is handed in, not built: the rendered frames of kd6d/libs/render_source.py
+    (--frame_source render).  The sampler runs over the store's slots (shuffled and dropping the last partial batch when
+    `training`, DistributedSampler semantics under torch.distributed), and everything after it -- the DZI jitter from
+    numpy's global stream, kd6d_dzi_crop, AugmentFront with --augment, the device pose remap -- is CachedDziLoader's,
+    unchanged.  `.loader.dataset` has the `meshes` / `bbox_3d` dataset_meshes and vsd_setup read.  refresh_every_epoch:
+    the store is redrawn and re-rendered after each pass (train_kd.py --render_refresh epoch)."""
+
+    def __init__(self, store, cfg, device, training, batch_size, augment=False, distributed=False, refresh_every_epoch=False):
+        from torch.utils.data import DataLoader
+        dset = store.dataset
+        if distributed:
+            smp = D.DistributedSampler(dset, shuffle=training)
+        elif training:
+            smp = torch.utils.data.RandomSampler(dset)
+        else:
+            smp = torch.utils.data.SequentialSampler(dset)
+        loader = DataLoader(dset, batch_size=int(batch_size), sampler=smp, num_workers=0, collate_fn=list,
+                            drop_last=bool(training))
+        super().__init__(loader, cfg, device, training, augment=augment, cache=store)
+        self.refresh_every_epoch = bool(refresh_every_epoch)
+
+    def __iter__(self):
+        yield from super().__iter__()
+        if self.refresh_every_epoch:
+            self.cache.refresh()
+
+
+RENDER_TRAIN_LIST, RENDER_VALID_LIST = 0, 1     # the last element of a rendered list's seed sequence (seed, rank, list)
+
+
+def build_rendered_dataset(cfg, device="cuda", augment=False, training=True, render_fn=None, log=print):
+    """--frame_source render: -> (train RenderedDziLoader or None, valid RenderedDziLoader) over frames drawn by
+    csrc/render_frames.hip (kd6d/libs/render_source.py) at INPUT.INTERNAL_* under INPUT.INTERNAL_K.  RUNTIME keys:
+    RENDER_MESHES (dataset: the PLYs of DATASETS.MESH_DIR with DATASETS.BBOX_FILE; surrogate: synthetic.surrogate_mesh
+    with cube_keypoints), RENDER_FRAMES / RENDER_VALID_FRAMES, RENDER_INSTANCES, RENDER_REFRESH, RENDER_BACKGROUNDS,
+    RENDER_SEED (the training list is seeded with the sequence (seed, rank, 0): every rank renders its own frames; the valid
+    list with (seed, 0, 1), the same on every rank and never refreshed), RENDER_CLASSES (default: class 0 alone for one
+    instance per frame, the LINEMOD classes otherwise; every class with `dataset` meshes), FRAME_CACHE_GB (the budget of
+    each list).  training=False (test.py): the valid list alone."""
+    from . import render_source as RS
+    rt, ds = cfg["RUNTIME"], cfg["DATASETS"]
+    H, W = int(cfg["INPUT"]["INTERNAL_HEIGHT"]), int(cfg["INPUT"]["INTERNAL_WIDTH"])
+    K = np.asarray(cfg["INPUT"]["INTERNAL_K"], np.float64).reshape(3, 3)
+    kind = rt.get("RENDER_MESHES", "surrogate")
+    inst = int(rt.get("RENDER_INSTANCES", 1))
+    if kind == "dataset":
+        from .dataset import load_bbox_3d
+        meshes = RS.dataset_meshes_colored(ds["MESH_DIR"])
+        kp3d = torch.tensor(load_bbox_3d(ds["BBOX_FILE"]), dtype=torch.float32)
+        classes = rt.get("RENDER_CLASSES") or list(range(min(len(meshes), len(kp3d))))
+    elif kind == "surrogate":
+        from ..synthetic import LINEMOD_CLASSES
+        diam = ds.get("MESH_DIAMETERS")
+        meshes, kp3d = RS.surrogate_meshes(int(ds["N_CLASS"]) - 1, int(rt.get("RENDER_SURROGATE_LEVEL", 4)), diam)
+        classes = rt.get("RENDER_CLASSES") or ([0] if inst == 1 else [c for c in LINEMOD_CLASSES if c < len(meshes)])
+    else:
+        raise ValueError("RENDER_MESHES must be dataset or surrogate (got %r)" % (kind,))
+    rank = D.get_rank() if rt.get("DISTRIBUTED", False) else 0
+    seed = int(rt.get("RENDER_SEED", 0))
+    budget = int(float(rt.get("FRAME_CACHE_GB", 64.)) * 2 ** 30)
+    common = dict(instances=inst, classes=classes, backgrounds=rt.get("RENDER_BACKGROUNDS", "noise"), budget_bytes=budget,
+                  render_fn=render_fn, log=log)
+    train = None
+    if training:
+        store = RS.RenderedFrames(meshes, kp3d, int(rt.get("RENDER_FRAMES", 2048)), K, H, W, device, seed=(seed, rank, RENDER_TRAIN_LIST), training=True,
+                                  tag="render_train", **common)
+        train = RenderedDziLoader(store, cfg, device, True, D.shard_batch(cfg["SOLVER"]["IMS_PER_BATCH"]), augment=bool(augment),
+                                  refresh_every_epoch=rt.get("RENDER_REFRESH", "epoch") == "epoch")
+        per_gpu = D.shard_batch(cfg["SOLVER"]["IMS_PER_BATCH"])
+    else:
+        per_gpu = int(cfg.get("TEST", {}).get("IMS_PER_BATCH", cfg["SOLVER"]["IMS_PER_BATCH"]))
+    vstore = RS.RenderedFrames(meshes, kp3d, int(rt.get("RENDER_VALID_FRAMES", 256)), K, H, W, device,
+                               seed=(seed, 0, RENDER_VALID_LIST), training=False, tag="render_valid",
+                               keep_depth=bool(rt.get("BOP_VSD", False)), **common)
+    # the valid list is the same on every rank (a fixed seed, no rank in it): the ranks share it out like a listed one;
+    # a rank's training frames are its own, so its sampler runs over all of them
+    return train, RenderedDziLoader(vstore, cfg, device, False, per_gpu, distributed=bool(rt.get("DISTRIBUTED", False)))
 
 
 FRAME_CACHE_MODES = ("off", "device")
@@ -371,6 +454,8 @@ def vsd_setup(cfg, loader, meshes, device):
                                            int(cfg["INPUT"].get("INTERNAL_WIDTH", 640)))
     dset = loader.loader.dataset
     dset = dset.datasets[0] if hasattr(dset, "datasets") else dset
+    if hasattr(dset, "rendered_depth"):                  # --frame_source render: D_test is the depth the renderer wrote
+        return list(dset.meshes), dset.rendered_depth
     cache = {}
     return list(dset.meshes), lambda meta: load_depth_mm(meta["path"], cache)
 

@@ -915,6 +915,79 @@ def bop_vsd(verts, faces, voff, vcnt, foff, fcnt, K, Rg, Tg, Rp, Tp, diameter, f
     return counts, err
 
 
+RENDER_MAX_SLOTS = 4                 # KD6D_MAX_GT: objects one rendered frame shows
+RENDER_MAX_FACES = 1 << 28           # faces of one item (the owner id keeps 28 bits for the face)
+
+
+def render_frames(verts, faces, vcol, voff, vcnt, foff, fcnt, item_frame, item_slot, R, T, K, light, ambient, bg_index,
+                  backgrounds, height, width, want_depth=False, out=None, validate=True):
+    """Shaded colour frames with their visible-instance masks in one call (csrc/render_frames.hip; the float64
+    definition is kd6d.libs.render.render_frames_host).  verts (Nv, 3) fp32, faces (Nf, 3) int32 relative to the item's
+    voff, vcol (Nv, 3) uint8 RGB; per item voff, vcnt, foff, fcnt, item_frame, item_slot (n_items,) int32, R
+    (n_items, 3, 3), T (n_items, 3) fp32; per frame K (n, 3, 3), light (n, 3), ambient (n,) fp32, bg_index (n,) int32;
+    backgrounds (n_bg, height, width, 3) uint8 (BGR, copied as they are).
+    -> frames (n, height, width, 3) uint8 BGR, masks (n, height, width) uint8 (0 = background, slot + 1 = the object that
+    owns the pixel), depth (n, height, width) fp32 or None (want_depth).  out: (frames, masks, depth or None) to write into.
+    validate: check on the device that every offset, count, face index, frame, slot and background index stays in its
+    range and that no two items claim one (frame, slot), and read the verdict back (ONE synchronisation); nothing is
+    launched when it fails."""
+    n = K.numel() // 9
+    n_items = voff.numel()
+    dev = K.device
+    H, W = int(height), int(width)
+    _mesh_items_assert("render_frames", verts, faces, voff, vcnt, foff, fcnt, n_items)
+    assert vcol.dtype == torch.uint8 and vcol.shape == verts.shape, "render_frames: vcol is (Nv, 3) uint8"
+    for t in (item_frame, item_slot):
+        assert t.dtype == torch.int32 and t.numel() == n_items
+    for t, k, m in ((R, 9, n_items), (T, 3, n_items), (K, 9, n), (light, 3, n), (ambient, 1, n)):
+        assert t.dtype == torch.float32 and t.numel() == m * k and t.is_contiguous()
+    assert bg_index.dtype == torch.int32 and bg_index.numel() == n
+    assert backgrounds.dtype == torch.uint8 and backgrounds.dim() == 4 and tuple(backgrounds.shape[1:]) == (H, W, 3) and \
+        backgrounds.is_contiguous(), "render_frames: backgrounds is (n_bg, %d, %d, 3) uint8" % (H, W)
+    n_bg = backgrounds.shape[0]
+    if out is None:
+        out = (torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev), torch.empty(n, H, W, dtype=torch.uint8, device=dev),
+               torch.empty(n, H, W, dtype=torch.float32, device=dev) if want_depth else None)
+    frames, masks, depth = out
+    assert frames.dtype == torch.uint8 and tuple(frames.shape) == (n, H, W, 3) and frames.is_contiguous()
+    assert masks.dtype == torch.uint8 and tuple(masks.shape) == (n, H, W) and masks.is_contiguous()
+    assert depth is None or (depth.dtype == torch.float32 and tuple(depth.shape) == (n, H, W) and depth.is_contiguous())
+    if n == 0:
+        return frames, masks, depth
+    if validate:
+        checks = [(bg_index < 0) | (bg_index >= n_bg)]
+        if n_items:
+            bad, bad_face = _mesh_items_check(verts, faces, voff, vcnt, foff, fcnt)
+            bad_fs = (item_frame < 0) | (item_frame >= n) | (item_slot < 0) | (item_slot >= RENDER_MAX_SLOTS)
+            key = (item_frame.long() * RENDER_MAX_SLOTS + item_slot.long()).clamp(0, n * RENDER_MAX_SLOTS - 1)
+            twice = torch.zeros(n * RENDER_MAX_SLOTS, dtype=torch.int32, device=dev).index_add_(0, key, (~bad_fs).int()) > 1
+            checks += [bad | (fcnt >= RENDER_MAX_FACES), bad_face, bad_fs, twice]
+        verdict = torch.stack([c.any() for c in checks]).tolist()                      # the one synchronisation
+        if verdict[0]:
+            raise ValueError("render_frames: frame %d points outside the pool of %d backgrounds"
+                             % (int(torch.nonzero(checks[0])[0]), n_bg))
+        if n_items and verdict[1]:
+            raise ValueError("render_frames: item %d points outside the pools of %d vertices and %d faces"
+                             % (int(torch.nonzero(checks[1])[0]), verts.shape[0], faces.shape[0]))
+        if n_items and verdict[2]:
+            raise ValueError("render_frames: item %d has a face index outside its vcnt vertices"
+                             % int(torch.nonzero(checks[2])[0]))
+        if n_items and verdict[3]:
+            raise ValueError("render_frames: item %d has a frame outside [0, %d) or a slot outside [0, %d)"
+                             % (int(torch.nonzero(checks[3])[0]), n, RENDER_MAX_SLOTS))
+        if n_items and verdict[4]:
+            at = int(torch.nonzero(checks[4])[0])
+            raise ValueError("render_frames: two items claim slot %d of frame %d" % (at % RENDER_MAX_SLOTS, at // RENDER_MAX_SLOTS))
+    nws = int(lib.kd6d_render_frames_workspace_ints(n, n_items))
+    ws = torch.empty(nws, dtype=torch.int32, device=dev)
+    check(lib.kd6d_render_frames(n, n_items, _ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], _ptr(vcol),
+                                 _ptr(voff), _ptr(vcnt), _ptr(foff), _ptr(fcnt), _ptr(item_frame), _ptr(item_slot),
+                                 _ptr(R), _ptr(T), _ptr(K), _ptr(light), _ptr(ambient), _ptr(bg_index),
+                                 _ptr(backgrounds), int(n_bg), H, W, _ptr(ws), nws, _ptr(frames), _ptr(masks),
+                                 _ptr(depth) if depth is not None else None, _stream()), "kd6d_render_frames")
+    return frames, masks, depth
+
+
 def sinkhorn_dense(x, alpha, y, beta, blur=0.05, scaling=0.5, reach=0.5, diameter=None, p=2.0):
     """Debiased (unbalanced) Sinkhorn divergence between two LARGE weighted point sets: x (N,D), alpha (N),
     y (M,D), beta (M), D in {2,4,8,16} -- losses/kd_loss.py:26-30 / loss_libs.py:47 with a dense grid of local

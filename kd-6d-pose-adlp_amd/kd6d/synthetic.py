@@ -130,3 +130,45 @@ def make_batch(batch, seed, crop=256, mixed_classes=False, full_frame=False, cla
                                  torch.from_numpy(T[None].copy()), W, H,
                                  torch.tensor(float(s)), torch.from_numpy(bbox_trans)))
     return ImageList(torch.from_numpy(imgs), [(H, W)] * batch), targets
+
+
+def _icosphere(level):
+    """Unit icosphere: 12 vertices / 20 faces, each subdivision splits a face in four (level 4: 2562 / 5120)."""
+    t = (1.0 + math.sqrt(5.0)) / 2.0
+    v = [[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+         [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]]
+    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6],
+         [7, 1, 8], [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7],
+         [9, 8, 1]]
+    for _ in range(level):
+        mid, nf = {}, []
+        for a, b, c in f:
+            m = []
+            for i, j in ((a, b), (b, c), (c, a)):
+                key = (min(i, j), max(i, j))
+                if key not in mid:
+                    p = v[i] + v[j]
+                    v.append(p / np.linalg.norm(p))
+                    mid[key] = len(v) - 1
+                m.append(mid[key])
+            nf += [[a, m[0], m[2]], [b, m[1], m[0]], [c, m[2], m[1]], m]
+        f = nf
+    return np.asarray(v, np.float64), np.asarray(f, np.int32)
+
+
+SURROGATE_AXES = (1.0, 0.72, 0.5)       # semi-axes of surrogate_mesh in units of the half edge of the class's cube
+
+
+def surrogate_mesh(class_id, level=4, diameters=MESH_DIAMETERS):
+    """A mesh to RENDER for class `class_id` when no model file is read (--render_meshes surrogate): a subdivided
+    ellipsoid with three different semi-axes, inscribed in the class's cube_keypoints box, coloured by a smooth function
+    of the vertex position that no symmetry of the ellipsoid preserves -- no pose is ambiguous in colour or outline.
+    -> (vertices (n, 3) float32, faces (m, 3) int32, colors (n, 3) uint8 RGB); level 4: 2562 vertices, 5120 faces."""
+    s, f = _icosphere(int(level))
+    e = float(diameters[int(class_id)]) / (2.0 * math.sqrt(3.0))
+    v = s * (np.asarray(SURROGATE_AXES, np.float64) * e)[None]
+    ph = 0.7 * int(class_id)
+    c = np.stack([128 + 100 * np.sin(2.4 * s[:, 0] + 1.1 * s[:, 1] + ph), 128 + 100 * np.sin(2.9 * s[:, 1] - 1.3 * s[:, 2] + 1.0 + ph),
+                  128 + 100 * np.sin(2.2 * s[:, 2] + 1.7 * s[:, 0] * s[:, 1] + 2.0 + ph)], axis=1)
+    return v.astype(np.float32), f, np.clip(np.rint(c), 0, 255).astype(np.uint8)

@@ -3,7 +3,7 @@ checkpoint without starting a training run.
 
     python test.py --config_file ./configs/ape.yaml --backbone darknet_tiny_h --weight_file outputs/ape/kd/final.pth \
         --working_dir outputs/ape/test/ --pnp_solver device --eval_scorer device [--test_file list.txt | --synthetic]
-        [--frame_cache device] [--bop_metrics [--bop_vsd]] [--bop_csv results.csv]
+        [--frame_cache device | --frame_source render] [--bop_metrics [--bop_vsd]] [--bop_csv results.csv]
 
 Builds the network named by --backbone, loads --weight_file (a bare state dict or one under a 'model' key, loosely by
 name as the reference does; says whether weights were loaded or are random), builds the valid-style loader over
@@ -88,6 +88,12 @@ def main(argv=None):
     if cfg["RUNTIME"]["SYNTHETIC"]:
         from train_kd import synthetic_valid_loader
         loader, meshes = synthetic_valid_loader(cfg, device)
+    elif cfg["RUNTIME"].get("FRAME_SOURCE", "list") == "render":  # the rendered valid list train_kd.py validates on
+        if cfg["RUNTIME"].get("BOP_CSV", ""):
+            raise SystemExit("--bop_csv cannot be combined with --frame_source render: rendered frames have no BOP scene / image ids")
+        from kd6d.libs.train_libs import build_rendered_dataset
+        loader = build_rendered_dataset(cfg, device, training=False)[1]
+        meshes = dataset_meshes(loader)
     else:
         loader = build_test_dataset(cfg, device, frame_cache=cfg["RUNTIME"].get("FRAME_CACHE", "off"),
                                     frame_cache_gb=cfg["RUNTIME"].get("FRAME_CACHE_GB", 64.))

@@ -10,7 +10,8 @@ GPU; the gradient exchange goes through kd6d_comm_* = librccl over xGMI).  Witho
 image lists of the yaml are read (kd6d/libs/train_libs.build_dataset: frames at the internal resolution, the
 Dynamic-Zoom-In crop + normalisation run on the GPU; --augment adds the reference's train transform chain, Resize to
 INTERNAL_K included, on the GPU front-end; --frame_cache device decodes every frame once and keeps the lists in device
-memory, kd6d/libs/frame_cache.py); with it, seeded LINEMOD-shaped batches.  As in the
+memory, kd6d/libs/frame_cache.py; --frame_source render draws the frames on the GPU instead of reading lists,
+kd6d/libs/render_source.py); with it, seeded LINEMOD-shaped batches.  As in the
 reference the teacher is validated once before training (skip with --skip_teacher_eval) and every VAL_FREQ steps
 rank 0 validates the student (kd6d/libs/eval_libs.valid: eval forward -> pose candidates -> PnP-RANSAC -> ADI /
 REP; --eval_scorer device scores the poses in one launch; --bop_metrics adds BOP's MSSD / MSPD average recalls of every
@@ -154,10 +155,14 @@ if __name__ == "__main__":
         train_loader = synthetic_loader(cfg, device)
         valid_loader, valid_meshes = synthetic_valid_loader(cfg, device)
     else:
-        train_loader, valid_loader = build_dataset(cfg, device,                # train_kd.py:57 of the reference
-                                                   augment=cfg["RUNTIME"].get("AUGMENT", False),
-                                                   frame_cache=cfg["RUNTIME"].get("FRAME_CACHE", "off"),
-                                                   frame_cache_gb=cfg["RUNTIME"].get("FRAME_CACHE_GB", 64.))
+        if cfg["RUNTIME"].get("FRAME_SOURCE", "list") == "render":             # frames drawn by csrc/render_frames.hip
+            from kd6d.libs.train_libs import build_rendered_dataset
+            train_loader, valid_loader = build_rendered_dataset(cfg, device, augment=cfg["RUNTIME"].get("AUGMENT", False))
+        else:
+            train_loader, valid_loader = build_dataset(cfg, device,                # train_kd.py:57 of the reference
+                                                       augment=cfg["RUNTIME"].get("AUGMENT", False),
+                                                       frame_cache=cfg["RUNTIME"].get("FRAME_CACHE", "off"),
+                                                       frame_cache_gb=cfg["RUNTIME"].get("FRAME_CACHE_GB", 64.))
         valid_meshes = dataset_meshes(valid_loader)
 
         def epochs(loader):                                                    # the reference loops `while True` over epochs
