@@ -821,6 +821,30 @@ int kd6d_aug_filter(const uint8_t* src, uint8_t* dst, int B, int H, int W, const
                     int gray, uint64_t key, void* stream);
 int kd6d_aug_relabel(float* masks, int B, int H, int W, const float* lut, int max_id, void* stream);
 
+/* ---- the two remaining stages of the train transform chain (csrc/augment.hip; added under ABI 11, new symbols
+ * only; train_kd.py --aug_chain full).  Restatements like the stages above: parity unpinned at the cv2 boundary,
+ * the same arithmetic in numpy in tests/augment_full_ref.py.
+ * kd6d_aug_background  RandomBackground / merge_background_mask, in place on frames; masks are read only.  Image b with
+ *                      bg_index[b] = i in [0, n_bg): every pixel whose mask value is exactly 0 takes the pixel of
+ *                      cv2.resize(background i, (W, H)), 8-bit INTER_LINEAR with 11-bit coefficients (the integer recipe
+ *                      stands at the kernel), gathered from `pool`: n_bg BGR uint8 images at their native sizes in one
+ *                      buffer of pool_bytes, image i = bg_hw[2i] x bg_hw[2i+1] pixels at byte bg_off[i].  A background
+ *                      of the frame's size is copied exactly.  bg_index[b] = -1: untouched.  Defined no-ops, nothing
+ *                      dereferenced: an index outside [-1, n_bg), h or w < 1 (or > 32768), off < 0 or
+ *                      off + h*w*3 > pool_bytes.  The reference's alpha-channel merge is not built (frames are 3-channel).
+ * kd6d_aug_sharpen     RandomPencilSharpen, src -> dst (distinct).  Per image: ksize (B) int32 in {0, 5, 7, 9, 11}
+ *                      (0, and any other value, copies the image), mode (B) int32 (non-zero: edge = img / (blur + 0.01),
+ *                      zero: img - blur, float32), alpha (B) double.  edge -> uint8 by cv2.normalize(NORM_MINMAX, 0, 255)
+ *                      over all pixels and channels, blended img * (1 - alpha) + e * alpha in double, normalised again.
+ *                      The whole-image extrema are merged with integer atomic min / max on order-preserving encodings
+ *                      (exact in any order: reproducible).  ws: kd6d_aug_sharpen_ws_bytes(B) bytes, 8-byte aligned,
+ *                      initialised inside the call. */
+int kd6d_aug_background(uint8_t* frames, const float* masks, int B, int H, int W, const uint8_t* pool, int64_t pool_bytes,
+                        const int64_t* bg_off, const int32_t* bg_hw, int n_bg, const int32_t* bg_index, void* stream);
+int64_t kd6d_aug_sharpen_ws_bytes(int B);
+int kd6d_aug_sharpen(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ksize, const int32_t* mode,
+                     const double* alpha, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- optimiser: replaces clip_grad_norm_ + AdamW.step of train_kd.py:138-139 on one flat buffer.
  * kd6d_sumsq writes KD6D_SUMSQ_PARTS partial sums of x^2 (one per workgroup, unused slots zeroed; no atomics);
  * kd6d_clip_adamw adds them in a fixed order (reproducible), writes the total to *gnorm_sq_out (optional) and applies

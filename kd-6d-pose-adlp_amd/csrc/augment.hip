@@ -8,11 +8,17 @@
 //   kd6d_aug_mask_stats   per image and instance id: area + visible box (to_visible_boxlist / remove_invalids)
 //   kd6d_aug_occlude      RandomOcclusion: rectangles from the visible boxes and five host uniforms per slot,
 //                         random bytes into the frame, -1 into the mask
+//   kd6d_aug_background   RandomBackground (--aug_chain full): mask == 0 pixels take cv2.resize(back, frame size),
+//                         8-bit INTER_LINEAR gathered from a pool of backgrounds at their native sizes (in place)
+//   kd6d_aug_warp_u8      (RandomShiftScaleRotate, as above)
 //   kd6d_aug_hsv          RandomHSV: cv2 8-bit BGR->HSV, float32 scale, truncating store, HSV->BGR (in place)
+//   kd6d_aug_sharpen      RandomPencilSharpen (--aug_chain full): box blur on LDS tiles, edge image, two whole-image
+//                         min-max normalisations (init + three launches)
 //   kd6d_aug_filter       RandomSmooth (cv2.blur, BORDER_REFLECT_101) + RandomNoise + Grayscalize, fused
 //   kd6d_aug_relabel      remove_invalids: per-image id lookup table on the mask
 //
-// One thread per output pixel, all three channels.  Everything is HBM / latency bound: plain loads and
+// The reference chain's eight pixel stages are all here.  One thread per output pixel, all three channels, except in
+// kd6d_aug_sharpen (one thread per value, LDS tiles).  The others are HBM / latency bound: plain loads and
 // stores, no LDS tiling, no matrix pipe.  Per-pixel randomness (occlusion bytes, Gaussian noise) is a
 // counter-based hash of (key, image, pixel, channel): order-free, so the result does not depend on the
 // launch shape.  The arithmetic restates OpenCV's documented 8-bit fixed-point scheme (parity unpinned: no
@@ -368,6 +374,277 @@ __global__ __launch_bounds__(256) void relabel_kernel(float* __restrict__ masks,
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// RandomBackground (transform.py:130-190, merge_background_mask): a pixel whose mask value is exactly 0 takes the
+// pixel of cv2.resize(back, (W, H)), every other pixel keeps its byte (np.uint8(back * (1 - a) + fore * a) with a in
+// {0, 1} is that selection).  The resize is computed here, per output pixel, as a four-tap gather from the ragged pool
+// of backgrounds at their native sizes; no resized copy exists.  cv2's 8-bit INTER_LINEAR, restated per axis
+// (d = output index, n = source extent, N = output extent):
+//     f  = float32((d + 0.5) * (double(n) / double(N)) - 0.5)       (double arithmetic, rounded once to float32)
+//     s  = floor(f);  f = f - float32(s)                            (float32)
+//     s < 0      -> s = 0,     f = 0;      s >= n - 1 -> s = n - 1, f = 0;      taps s and min(s + 1, n - 1)
+//     c0 = rint((1 - f) * 2048),  c1 = rint(f * 2048)               (float32, ties to even: the 11-bit coefficients)
+// horizontal pass, per source row:   h = p[x0] * a0 + p[x1] * a1                             (int, scaled by 2^11)
+// vertical pass:                     out = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2
+// A background of the frame's size has f = 0 everywhere: (2048 * (p * 128)) >> 16 = 4 p, (4 p + 2) >> 2 = p, a copy.
+// (cv2 switches an exact 2x downscale to its area path; this restatement stays bilinear at every scale.)
+// Bad input is a no-op, never dereferenced: an index outside [0, n_bg) (-1 = "no background"), or a table entry
+// with h, w < 1 or off + h * w * 3 > pool_bytes, leaves the image untouched.
+constexpr int RESIZE_COEF_BITS = 11;
+constexpr int BG_MAX_SIDE = 32768;            // keeps h * w * 3 far inside 64 bits
+
+__device__ __forceinline__ void resize_taps(int d, double scale, int n, int* i0, int* i1, int* c0, int* c1) {
+#pragma clang fp contract(off)
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f = f - (float)s;
+  if (s < 0) { s = 0; f = 0.f; }
+  if (s >= n - 1) { s = n - 1; f = 0.f; }
+  *i0 = s;
+  *i1 = s + 1 < n ? s + 1 : n - 1;
+  *c0 = (int)rintf((1.f - f) * (float)(1 << RESIZE_COEF_BITS));
+  *c1 = (int)rintf(f * (float)(1 << RESIZE_COEF_BITS));
+}
+
+__global__ __launch_bounds__(256) void background_kernel(unsigned char* __restrict__ frames,
+                                                         const float* __restrict__ masks, int H, int W,
+                                                         const unsigned char* __restrict__ pool, long long pool_bytes,
+                                                         const long long* __restrict__ bg_off,
+                                                         const int* __restrict__ bg_hw, int n_bg,
+                                                         const int* __restrict__ bg_index) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y;
+  const int idx = bg_index[b];
+  if (idx < 0 || idx >= n_bg) return;
+  const int h = bg_hw[idx * 2], w = bg_hw[idx * 2 + 1];
+  const long long off = bg_off[idx];
+  if (h < 1 || w < 1 || h > BG_MAX_SIDE || w > BG_MAX_SIDE || off < 0 || off > pool_bytes ||
+      (long long)h * w * 3 > pool_bytes - off)
+    return;
+  const unsigned char* bg = pool + off;
+  const double sx = (double)w / (double)W, sy = (double)h / (double)H;
+  const long long npix = (long long)H * W;
+  const float* mk = masks + (size_t)b * npix;
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long long)gridDim.x * 256) {
+    if (!(mk[p] == 0.f)) continue;
+    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    int x0, x1, a0, a1, y0, y1, b0, b1;
+    resize_taps(x, sx, w, &x0, &x1, &a0, &a1);
+    resize_taps(y, sy, h, &y0, &y1, &b0, &b1);
+    const unsigned char* r0 = bg + (size_t)y0 * w * 3;
+    const unsigned char* r1 = bg + (size_t)y1 * w * 3;
+    unsigned char* o = frames + ((size_t)b * npix + (size_t)p) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int h0 = r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1;
+      const int h1 = r1[x0 * 3 + c] * a0 + r1[x1 * 3 + c] * a1;
+      o[c] = (unsigned char)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// RandomPencilSharpen (transform.py:111-128) with the reference's dtypes, per image with ks in {5, 7, 9, 11}:
+//   s    = cv2.blur(img, (ks, ks))                              filter_kernel's arithmetic (REFLECT_101, rounded mean)
+//   edge = img / (float32(s) + 0.01f)   (mode != 0)             float32, IEEE division
+//        = img - float32(s)             (mode == 0)
+//   e    = uint8(edge * float32(scale) + float32(shift))        cv2.normalize(NORM_MINMAX, 0, 255) of a float32 image:
+//          scale = 255 * (max - min > DBL_EPSILON ? 1 / (max - min) : 0),  shift = 0 - min * scale, both in double,
+//          applied in float32, truncated
+//   v    = img * (1 - alpha) + e * alpha                        float64
+//   out  = uint8(v * scale' + shift')                           the same normalisation of v, applied in double, truncated
+// ks = 0 (and any size this kernel does not take) copies the image.  The two whole-image extrema need three passes:
+//   a  blur, edge, min / max of edge;      b  blur, edge, e (parked in dst), v, min / max of v;      c  out from src, e.
+// Passes a and b work on SH_TH x SH_TW tiles: the tile and its reflected halo are staged once in LDS as bytes, the
+// ks horizontal sums of every staged row go to a second LDS plane (uint16: at most 11 * 255), and a value's box sum is
+// ks reads down that plane -- 2 ks LDS reads per value where filter_kernel issues ks^2 global byte loads.  A thread
+// owns one (pixel, channel) VALUE at a time, so consecutive lanes touch consecutive bytes / uint16 of both planes: a
+// 32-lane group covers at most 64 contiguous bytes (16 banks) of a row, and the plane of row sums has no padding
+// between rows, so a wave that straddles two rows still reads one contiguous run -- no bank is hit twice.
+// Extrema: per thread, then wave shuffles, then one LDS slot per wave, then ONE integer atomic min and max per
+// workgroup on an order-preserving encoding (float32 edge: sign flip; float64 v >= 0: its bits as uint64).  min / max
+// are exact in any order, so the result is a pure function of the image.
+constexpr int SH_TW = 32, SH_TH = 32, SH_RMAX = 5;
+constexpr int SH_RAW_PITCH = (SH_TW + 2 * SH_RMAX) * 3;      // bytes per staged row
+constexpr int SH_ROW_PITCH = SH_TW * 3;                      // uint16 per row of horizontal sums
+
+struct SharpenWs {                   // per image; kd6d_aug_sharpen_ws_bytes = sizeof * B
+  unsigned emin, emax;               // encoded float32 extrema of edge
+  unsigned long long vmin, vmax;     // bits of the float64 extrema of v (v >= 0)
+  unsigned long long pad;
+};
+
+__device__ __forceinline__ int sharpen_ks(int ks) { return (ks >= 5 && ks <= 2 * SH_RMAX + 1 && (ks & 1)) ? ks : 0; }
+
+__device__ __forceinline__ unsigned enc_f32(float f) {
+  const unsigned u = __float_as_uint(f);
+  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float dec_f32(unsigned e) {
+  return __uint_as_float(e ^ ((e >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+
+// cv2.normalize(NORM_MINMAX, alpha = 0, beta = 255): scale and shift in double
+__device__ __forceinline__ void minmax_scale(double mn, double mx, double* scale, double* shift) {
+#pragma clang fp contract(off)
+  const double d = mx - mn;
+  *scale = 255.0 * (d > 2.220446049250313e-16 ? 1.0 / d : 0.0);
+  *shift = 0.0 - mn * *scale;
+}
+
+__device__ __forceinline__ float sharpen_edge(int img, int blur, bool ratio) {
+#pragma clang fp contract(off)
+  return ratio ? (float)img / ((float)blur + 0.01f) : (float)img - (float)blur;
+}
+
+__device__ __forceinline__ int sharpen_e(float edge, float scale, float shift) {
+#pragma clang fp contract(off)
+  return (int)(edge * scale + shift) & 255;
+}
+
+__device__ __forceinline__ double sharpen_v(int img, int e, double alpha) {
+#pragma clang fp contract(off)
+  return (double)img * (1.0 - alpha) + (double)e * alpha;
+}
+
+template <int PASS, int KS>
+__device__ __forceinline__ void sharpen_tile(const unsigned char* __restrict__ fr, unsigned char* __restrict__ out, int H,
+                                             int W, bool ratio, double alpha, SharpenWs* __restrict__ ws,
+                                             unsigned char* s_raw, unsigned short* s_row, unsigned long long* s_red) {
+#pragma clang fp contract(off)
+  constexpr int R = KS / 2, AREA = KS * KS;
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * SH_TW, y0 = blockIdx.y * SH_TH;
+  const int tw = min(SH_TW, W - x0), th = min(SH_TH, H - y0);
+  const int cols = tw + 2 * R, rows = th + 2 * R;
+  for (int i = tid; i < rows * cols; i += 256) {
+    const int ry = i / cols, rx = i - ry * cols;
+    const unsigned char* q = fr + ((size_t)reflect101(y0 - R + ry, H) * W + (size_t)reflect101(x0 - R + rx, W)) * 3;
+    unsigned char* d = s_raw + ry * SH_RAW_PITCH + rx * 3;
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
+  }
+  __syncthreads();
+  const int vals = tw * 3;
+  for (int i = tid; i < rows * vals; i += 256) {
+    const int ry = i / vals, j = i - ry * vals;
+    const unsigned char* q = s_raw + ry * SH_RAW_PITCH + j;
+    int s = 0;
+#pragma unroll
+    for (int d = 0; d < KS; ++d) s += q[d * 3];
+    s_row[ry * SH_ROW_PITCH + j] = (unsigned short)s;
+  }
+  __syncthreads();
+  float scale = 0.f, shift = 0.f;
+  if (PASS == 2) {
+    double sc, sh;
+    minmax_scale((double)dec_f32(ws->emin), (double)dec_f32(ws->emax), &sc, &sh);
+    scale = (float)sc; shift = (float)sh;
+  }
+  float elo = INFINITY, ehi = -INFINITY;
+  double vlo = INFINITY, vhi = 0.0;
+  for (int i = tid; i < th * vals; i += 256) {
+    const int py = i / vals, j = i - py * vals;
+    const unsigned short* q = s_row + py * SH_ROW_PITCH + j;
+    int s = 0;
+#pragma unroll
+    for (int d = 0; d < KS; ++d) s += q[d * SH_ROW_PITCH];
+    const int blur = (s + AREA / 2) / AREA;
+    const int img = s_raw[(py + R) * SH_RAW_PITCH + R * 3 + j];
+    const float edge = sharpen_edge(img, blur, ratio);
+    if (PASS == 1) {
+      elo = fminf(elo, edge); ehi = fmaxf(ehi, edge);
+    } else {
+      const int e = sharpen_e(edge, scale, shift);
+      const double v = sharpen_v(img, e, alpha);
+      vlo = fmin(vlo, v); vhi = fmax(vhi, v);
+      out[((size_t)(y0 + py) * W + (size_t)x0) * 3 + j] = (unsigned char)e;
+    }
+  }
+  // workgroup extrema: shuffles inside a wave, one LDS slot per wave, one atomic pair per workgroup
+  unsigned long long lo, hi;
+  if (PASS == 1) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      elo = fminf(elo, __shfl_xor(elo, o, 64));
+      ehi = fmaxf(ehi, __shfl_xor(ehi, o, 64));
+    }
+    lo = enc_f32(elo); hi = enc_f32(ehi);
+  } else {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      vlo = fmin(vlo, __shfl_xor(vlo, o, 64));
+      vhi = fmax(vhi, __shfl_xor(vhi, o, 64));
+    }
+    lo = (unsigned long long)__double_as_longlong(vlo); hi = (unsigned long long)__double_as_longlong(vhi);
+  }
+  if ((tid & 63) == 0) { s_red[(tid >> 6) * 2] = lo; s_red[(tid >> 6) * 2 + 1] = hi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < 4; ++k) {
+      lo = s_red[k * 2] < lo ? s_red[k * 2] : lo;
+      hi = s_red[k * 2 + 1] > hi ? s_red[k * 2 + 1] : hi;
+    }
+    if (PASS == 1) {
+      atomicMin(&ws->emin, (unsigned)lo);
+      atomicMax(&ws->emax, (unsigned)hi);
+    } else {
+      atomicMin(&ws->vmin, lo);
+      atomicMax(&ws->vmax, hi);
+    }
+  }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void sharpen_tile_kernel(const unsigned char* __restrict__ src,
+                                                           unsigned char* __restrict__ dst, int H, int W,
+                                                           const int* __restrict__ ksize, const int* __restrict__ mode,
+                                                           const double* __restrict__ alpha,
+                                                           SharpenWs* __restrict__ ws) {
+  __shared__ unsigned char s_raw[(SH_TH + 2 * SH_RMAX) * SH_RAW_PITCH];
+  __shared__ unsigned short s_row[(SH_TH + 2 * SH_RMAX) * SH_ROW_PITCH];
+  __shared__ unsigned long long s_red[8];
+  const int b = blockIdx.z;
+  const int ks = sharpen_ks(ksize[b]);
+  if (ks == 0) return;
+  const size_t img = (size_t)b * H * W * 3;
+  const bool ratio = mode[b] != 0;
+  const double a = alpha[b];
+  switch (ks) {
+    case 5: sharpen_tile<PASS, 5>(src + img, dst + img, H, W, ratio, a, ws + b, s_raw, s_row, s_red); break;
+    case 7: sharpen_tile<PASS, 7>(src + img, dst + img, H, W, ratio, a, ws + b, s_raw, s_row, s_red); break;
+    case 9: sharpen_tile<PASS, 9>(src + img, dst + img, H, W, ratio, a, ws + b, s_raw, s_row, s_red); break;
+    default: sharpen_tile<PASS, 11>(src + img, dst + img, H, W, ratio, a, ws + b, s_raw, s_row, s_red); break;
+  }
+}
+
+__global__ void sharpen_init_kernel(SharpenWs* __restrict__ ws, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  ws[b].emin = 0xFFFFFFFFu; ws[b].emax = 0u;
+  ws[b].vmin = ~0ull; ws[b].vmax = 0ull; ws[b].pad = 0ull;
+}
+
+// pass c: per value, out = uint8(v * scale' + shift') from the source byte and the e parked in dst; ks = 0 copies
+__global__ __launch_bounds__(256) void sharpen_store_kernel(const unsigned char* __restrict__ src,
+                                                            unsigned char* __restrict__ dst, long long nval,
+                                                            const int* __restrict__ ksize,
+                                                            const double* __restrict__ alpha,
+                                                            const SharpenWs* __restrict__ ws) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y;
+  const unsigned char* s = src + (size_t)b * nval;
+  unsigned char* d = dst + (size_t)b * nval;
+  const bool on = sharpen_ks(ksize[b]) != 0;
+  double scale = 0.0, shift = 0.0;
+  if (on) minmax_scale(__longlong_as_double((long long)ws[b].vmin), __longlong_as_double((long long)ws[b].vmax), &scale, &shift);
+  const double a = alpha[b];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nval; i += (long long)gridDim.x * 256) {
+    if (!on) { d[i] = s[i]; continue; }
+    const double v = sharpen_v(s[i], d[i], a);
+    d[i] = (unsigned char)((int)(v * scale + shift) & 255);
+  }
+}
+
 int grid_x(long long npix) {
   long long nb = (npix + 255) / 256;
   return (int)(nb > 1024 ? 1024 : nb);
@@ -455,5 +732,47 @@ extern "C" int kd6d_aug_relabel(float* masks, int B, int H, int W, const float* 
   hipLaunchKernelGGL(relabel_kernel, dim3(grid_x((long long)H * W), B), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), masks, H, W, lut, max_id);
   KD6D_CHECK_LAUNCH("kd6d_aug_relabel");
+  return KD6D_OK;
+}
+
+extern "C" int kd6d_aug_background(uint8_t* frames, const float* masks, int B, int H, int W, const uint8_t* pool,
+                                   int64_t pool_bytes, const int64_t* bg_off, const int32_t* bg_hw, int n_bg,
+                                   const int32_t* bg_index, void* stream) {
+  KD6D_CHECK_ARG(frames && masks && pool && bg_off && bg_hw && bg_index, "kd6d_aug_background: null pointer");
+  AUG_CHECK_SIZES("kd6d_aug_background", B, H, W);
+  KD6D_CHECK_ARG(n_bg >= 1 && pool_bytes >= 3, "kd6d_aug_background: empty pool (n_bg=%d, pool_bytes=%lld)", n_bg,
+                 (long long)pool_bytes);
+  hipLaunchKernelGGL(background_kernel, dim3(grid_x((long long)H * W), B), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), frames, masks, H, W, pool, (long long)pool_bytes,
+                     (const long long*)bg_off, (const int*)bg_hw, n_bg, (const int*)bg_index);
+  KD6D_CHECK_LAUNCH("kd6d_aug_background");
+  return KD6D_OK;
+}
+
+extern "C" int64_t kd6d_aug_sharpen_ws_bytes(int B) { return B > 0 ? (int64_t)sizeof(SharpenWs) * B : 0; }
+
+extern "C" int kd6d_aug_sharpen(const uint8_t* src, uint8_t* dst, int B, int H, int W, const int32_t* ksize,
+                                const int32_t* mode, const double* alpha, void* ws, int64_t ws_bytes, void* stream) {
+  KD6D_CHECK_ARG(src && dst && ksize && mode && alpha && ws, "kd6d_aug_sharpen: null pointer");
+  KD6D_CHECK_ARG((const void*)src != (const void*)dst, "kd6d_aug_sharpen: in-place sharpen is not supported");
+  AUG_CHECK_SIZES("kd6d_aug_sharpen", B, H, W);
+  KD6D_CHECK_ARG(ws_bytes >= kd6d_aug_sharpen_ws_bytes(B), "kd6d_aug_sharpen: workspace of %lld bytes, %lld needed",
+                 (long long)ws_bytes, (long long)kd6d_aug_sharpen_ws_bytes(B));
+  KD6D_CHECK_ARG(((uintptr_t)ws & 7) == 0, "kd6d_aug_sharpen: workspace must be 8-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  SharpenWs* w = reinterpret_cast<SharpenWs*>(ws);
+  hipLaunchKernelGGL(sharpen_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, w, B);
+  KD6D_CHECK_LAUNCH("kd6d_aug_sharpen (init)");
+  const dim3 tiles((W + SH_TW - 1) / SH_TW, (H + SH_TH - 1) / SH_TH, B);
+  hipLaunchKernelGGL(sharpen_tile_kernel<1>, tiles, dim3(256), 0, st, src, dst, H, W, (const int*)ksize,
+                     (const int*)mode, alpha, w);
+  KD6D_CHECK_LAUNCH("kd6d_aug_sharpen (edge extrema)");
+  hipLaunchKernelGGL(sharpen_tile_kernel<2>, tiles, dim3(256), 0, st, src, dst, H, W, (const int*)ksize,
+                     (const int*)mode, alpha, w);
+  KD6D_CHECK_LAUNCH("kd6d_aug_sharpen (blend extrema)");
+  const long long nval = (long long)H * W * 3;
+  hipLaunchKernelGGL(sharpen_store_kernel, dim3(grid_x(nval), B), dim3(256), 0, st, src, dst, nval, (const int*)ksize,
+                     alpha, (const SharpenWs*)w);
+  KD6D_CHECK_LAUNCH("kd6d_aug_sharpen (store)");
   return KD6D_OK;
 }

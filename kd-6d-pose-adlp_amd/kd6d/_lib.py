@@ -185,6 +185,9 @@ SIGNATURES = {
     "kd6d_aug_hsv": [_P, _I, _I, _I, _P, _P],
     "kd6d_aug_filter": [_P, _P, _I, _I, _I, _P, _P, _I, ctypes.c_uint64, _P],
     "kd6d_aug_relabel": [_P, _I, _I, _I, _P, _I, _P],
+    "kd6d_aug_background": [_P, _P, _I, _I, _I, _P, _I64, _P, _P, _I, _P, _P],
+    "kd6d_aug_sharpen_ws_bytes": [_I],
+    "kd6d_aug_sharpen": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P],
     "kd6d_sumsq": [_P, _I64, _P, _P],
     "kd6d_clip_adamw": [_P, _P, _P, _P, _I64, _P, _P, _D, _D, _D, _D, _D, _D, _I64, _P, _P, _P],
     "kd6d_set_hyper": [_P, _D, _D, _D, _I64, _P],
@@ -199,7 +202,8 @@ SIGNATURES = {
     "kd6d_comm_destroy": [_P],
 }
 _RESTYPE = {"kd6d_last_error": ctypes.c_char_p, "kd6d_ctx_current": ctypes.c_void_p,
-            "kd6d_bop_vsd_workspace_ints": ctypes.c_int64, "kd6d_render_frames_workspace_ints": ctypes.c_int64}
+            "kd6d_bop_vsd_workspace_ints": ctypes.c_int64, "kd6d_render_frames_workspace_ints": ctypes.c_int64,
+            "kd6d_aug_sharpen_ws_bytes": ctypes.c_int64}
 
 
 class Kd6dError(RuntimeError):

@@ -3,7 +3,7 @@
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
 overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
---synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --bop_metrics, --bop_vsd, --frame_source and
+--synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --aug_chain, --aug_background_gb, --bop_metrics, --bop_vsd, --frame_source and
 the --render_* flags; yaml files may name a `_BASE_` file.
 """
 import argparse
@@ -65,6 +65,15 @@ def get_argparser():
                         "numpy, two solves per instance when the item is drawn (kd6d/libs/pnp.py); device = HIP "
                         "(csrc/pnp.hip), every instance of a batch in one launch of the augmentation front-end, read back "
                         "with its area table")
+    p.add_argument("--aug_chain", type=str, default="base", choices=["base", "full"],
+                   help="--augment: base = the chain without RandomBackground and RandomPencilSharpen (a yaml that sets "
+                        "SOLVER.AUGMENTATION_BACKGROUND_DIR or AUGMENTATION_Sharpen is refused); full = both stages run on "
+                        "the GPU front-end when the yaml enables them (csrc/augment.hip: kd6d_aug_background, "
+                        "kd6d_aug_sharpen)")
+    p.add_argument("--aug_background_gb", type=float, default=8.,
+                   help="--aug_chain full: most GiB of device memory the decoded backgrounds of "
+                        "SOLVER.AUGMENTATION_BACKGROUND_DIR may take per process (kept at their native sizes); a "
+                        "directory that does not fit is refused")
     p.add_argument("--skip_teacher_eval", action="store_true")
     p.add_argument("--launch", type=str, default="graph", choices=["graph", "pipeline", "eager"],
                    help="graph: replay the captured step (hipGraph); pipeline: also overlap the teacher forward of "
@@ -211,6 +220,17 @@ def aug_pose_remap_runtime(args):
     return mode
 
 
+AUG_CHAIN_ERROR = "--aug_chain full needs --augment: without it no transform chain runs"
+
+
+def aug_chain_runtime(args):
+    """-> the RUNTIME keys of --aug_chain / --aug_background_gb; refuses --aug_chain full without --augment."""
+    chain = getattr(args, "aug_chain", "base")
+    if chain == "full" and not bool(getattr(args, "augment", False)):
+        raise ValueError(AUG_CHAIN_ERROR)
+    return dict(AUG_CHAIN=chain, AUG_BACKGROUND_GB=float(getattr(args, "aug_background_gb", 8.)))
+
+
 def load_yaml(path):
     """yaml -> dict.  A top-level `_BASE_: other.yaml` (path relative to the file; additive key of this build) is
     loaded first and the file's own sections are merged over it key by key."""
@@ -251,6 +271,7 @@ def build_cfgs(args):
     cfg["RUNTIME"]["SYNTHETIC"] = bool(args.synthetic)
     cfg["RUNTIME"]["AUGMENT"] = bool(getattr(args, "augment", False))
     cfg["RUNTIME"]["AUG_POSE_REMAP"] = aug_pose_remap_runtime(args)
+    cfg["RUNTIME"].update(aug_chain_runtime(args))
     cfg["RUNTIME"].update(frame_cache_runtime(args))
     cfg["RUNTIME"].update(render_runtime(args))
     cfg["RUNTIME"]["SKIP_TEACHER_EVAL"] = bool(args.skip_teacher_eval)

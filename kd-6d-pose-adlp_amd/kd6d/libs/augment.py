@@ -3,8 +3,10 @@
 
   1 Resize                  M = INTERNAL_K K^-1; skipped when M is the identity (then a cv2 warp is an exact copy)
   2 RandomOcclusion         AUGMENTATION_OCCLUSION
+  2b RandomBackground       AUGMENTATION_BACKGROUND_DIR (--aug_chain full only)
   3 RandomShiftScaleRotate  AUGMENTATION_SHIFT / _SCALE / _ROTATION
   4 RandomHSV               AUGMENTATION_ColorH / _ColorS / _ColorV
+  4b RandomPencilSharpen    AUGMENTATION_Sharpen (--aug_chain full only)
   5 RandomSmooth            AUGMENTATION_Smooth (largest box size)
   6 RandomNoise             AUGMENTATION_Noise
   7 Grayscalize             AUGMENTATION_Grayscalize
@@ -30,8 +32,22 @@ Deviations from the reference:
   * an image that keeps no instance after the chain falls back to its frame after Resize only, with its
     Resize-remapped pose (the reference draws another image instead);
   * per-pixel random bytes / noise come from a counter-based hash on the device, not numpy's stream.
-RandomBackground and RandomPencilSharpen are not rebuilt: enabling them raises NotImplementedError.
+RandomBackground and RandomPencilSharpen are opt-in: RUNTIME.AUG_CHAIN = "full" (train_kd.py --aug_chain full).  On the
+default "base" chain enabling them still raises NotImplementedError, and nothing is drawn for them.  On the full chain:
+  * `draw_params` draws, per item, RandomBackground's coin from numpy's global stream and its file index from `random`
+    (after the occlusion block), and RandomPencilSharpen's test, box size, mode and alpha from `random` (after HSV);
+  * `AugmentFront` decodes the background directory ONCE into a BackgroundPool (device memory, native sizes, budget
+    RUNTIME.AUG_BACKGROUND_GB) and kd6d_aug_background resizes while it samples; kd6d_aug_sharpen is the LDS-tiled
+    box filter with the two whole-image min-max normalisations;
+  * deviations: the directory is listed sorted and joined with os.path.join (the reference concatenates dir + name in
+    os.listdir order); a missing or empty directory is an error (the reference silently disables the stage); a file
+    that cannot be decoded is an error naming it (the reference draws another file); frames are 3-channel here (the
+    dataset's clean-up drops alpha), so the alpha-channel merge is not built; the resize stays bilinear at an exact 2x
+    downscale, where cv2 switches INTER_LINEAR to its area path; AUGMENTATION_Sharpen = 0 draws nothing (the reference
+    draws one random.random() and discards it).
+Both are restatements like warp / HSV / blur: parity unpinned at the cv2 boundary (tests/augment_full_ref.py).
 """
+import os
 import random
 
 import numpy as np
@@ -42,18 +58,47 @@ from .pnp import remap_pose
 
 MIN_AREA = 10
 POSE_REMAP_MODES = ("host", "device")
+AUG_CHAINS = ("base", "full")
+BACKGROUND_EXTS = (".png", ".jpg")
+SHARPEN_KS = (5, 7, 9, 11)            # RandomPencilSharpen's ks_candidates
+
+
+def list_backgrounds(directory):
+    """The .png / .jpg file names of a background directory, sorted (names only).  Missing or empty: ValueError."""
+    if not os.path.isdir(directory):
+        raise ValueError("SOLVER.AUGMENTATION_BACKGROUND_DIR: %s is not a directory" % (directory,))
+    names = sorted(f for f in os.listdir(directory) if f.endswith(BACKGROUND_EXTS))
+    if not names:
+        raise ValueError("SOLVER.AUGMENTATION_BACKGROUND_DIR: %s holds no .png / .jpg file" % (directory,))
+    return names
 
 
 class AugConfig:
-    """The augmentation keys of a yaml, with the reference's own enable guards."""
+    """The augmentation keys of a yaml, with the reference's own enable guards.  RUNTIME.AUG_CHAIN (train_kd.py
+    --aug_chain): "base" (default, also when RUNTIME or the key is absent) refuses AUGMENTATION_BACKGROUND_DIR and
+    AUGMENTATION_Sharpen; "full" honours them (None / 0 = that stage off).  The object holds names and numbers only,
+    so it pickles into loader workers; the pixels of the backgrounds live in AugmentFront's BackgroundPool."""
 
     def __init__(self, cfg):
         s, inp = cfg["SOLVER"], cfg["INPUT"]
-        if s.get("AUGMENTATION_BACKGROUND_DIR") is not None:
-            raise NotImplementedError("SOLVER.AUGMENTATION_BACKGROUND_DIR: RandomBackground is not rebuilt "
-                                      "for --augment")
-        if s.get("AUGMENTATION_Sharpen", 0):
-            raise NotImplementedError("SOLVER.AUGMENTATION_Sharpen: RandomPencilSharpen is not rebuilt for --augment")
+        rt = cfg.get("RUNTIME") or {}
+        self.chain = rt.get("AUG_CHAIN", "base") or "base"
+        if self.chain not in AUG_CHAINS:
+            raise ValueError("RUNTIME.AUG_CHAIN must be one of %s (got %r)" % (AUG_CHAINS, self.chain))
+        bg_dir, sharpen = s.get("AUGMENTATION_BACKGROUND_DIR"), s.get("AUGMENTATION_Sharpen", 0)
+        if self.chain == "base":
+            if bg_dir is not None:
+                raise NotImplementedError("SOLVER.AUGMENTATION_BACKGROUND_DIR: RandomBackground is not rebuilt "
+                                          "for --augment on the base chain; pass --aug_chain full")
+            if sharpen:
+                raise NotImplementedError("SOLVER.AUGMENTATION_Sharpen: RandomPencilSharpen is not rebuilt for --augment "
+                                          "on the base chain; pass --aug_chain full")
+        self.background_dir, self.background_files = None, []
+        if bg_dir is not None:
+            self.background_dir = str(bg_dir)
+            self.background_files = list_backgrounds(self.background_dir)
+        self.background_gb = float(rt.get("AUG_BACKGROUND_GB", 8.))
+        self.sharpen = float(sharpen or 0)
         self.K = np.array(inp["INTERNAL_K"], np.float64).reshape(3, 3)
         self.width, self.height = int(inp["INTERNAL_WIDTH"]), int(inp["INTERNAL_HEIGHT"])
         self.occlusion = float(s.get("AUGMENTATION_OCCLUSION", 0) or 0)
@@ -74,6 +119,14 @@ class AugConfig:
     @property
     def occlusion_on(self):
         return self.occlusion > 0
+
+    @property
+    def background_on(self):
+        return len(self.background_files) > 0
+
+    @property
+    def sharpen_on(self):
+        return self.sharpen > 0
 
     @property
     def ssr_on(self):
@@ -138,10 +191,12 @@ def remap_poses(K, class_ids, rotations, translations, bbox_3d, dst_K, M):
     return np.asarray(Rs, np.float32).reshape(-1, 3, 3), np.asarray(Ts, np.float32).reshape(-1, 3, 1)
 
 
-def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random):
+def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random, np_rng=np.random):
     """Everything random of one item, in the chain's order, and the two pose remaps.  -> dict.
     ac.pose_remap == "device": no remap is solved here; the item carries its source poses in double (`pose_src`) for
-    kd6d_pose_remap instead of R_resize / T_resize / R / T.  The draws are the same, in the same order."""
+    kd6d_pose_remap instead of R_resize / T_resize / R / T.  The draws are the same, in the same order.
+    np_rng: RandomBackground's coin comes from numpy's global stream in the reference (np.random.rand), its file
+    index from `random`.  With both stages of the full chain off nothing is drawn for them."""
     n = len(class_ids)
     if n > AUG_MAX_ID:
         raise ValueError("--augment handles at most %d instances per frame (got %d)" % (AUG_MAX_ID, n))
@@ -158,6 +213,9 @@ def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random):
         p["R_resize"], p["T_resize"] = remap_poses(K, class_ids, rotations, translations, bbox_3d, ac.K, Mr)
     if ac.occlusion_on:
         p["occl_u"] = np.array([[rng.random() for _ in range(5)] for _ in range(MAX_GT)], np.float64)
+    if ac.background_on:
+        coin = np_rng.rand()
+        p["bg"] = rng.randint(0, len(ac.background_files) - 1) if coin < 0.5 else -1
     if ac.ssr_on:
         Ms = shift_scale_rotate_matrix(ac.shift, ac.scale, ac.rotation, ac.width, ac.height, rng)
         p["M_ssr"] = Ms[:2].astype(np.float64)
@@ -167,6 +225,12 @@ def draw_params(ac, K, class_ids, rotations, translations, bbox_3d, rng=random):
         p["R"], p["T"] = p["R_resize"], p["T_resize"]
     if ac.hsv_on:
         p["hsv"] = np.array([rng.uniform(-1, 1) * r + 1 for r in ac.hsv], np.float32)
+    if ac.sharpen_on:
+        p["sharpen_ks"], p["sharpen_mode"], p["sharpen_alpha"] = 0, 0, 0.0
+        if rng.random() < ac.sharpen:
+            p["sharpen_ks"] = rng.choice(list(SHARPEN_KS))
+            p["sharpen_mode"] = int(rng.random() < 0.5)          # 1: edge = img / blur, 0: img - blur
+            p["sharpen_alpha"] = rng.uniform(0.5, 0.95)
     if ac.smooth_on:
         p["ksize"] = rng.choice(list(range(1, ac.smooth + 1, 2)))
     if ac.noise_on:
@@ -206,6 +270,12 @@ def collate_params(ps):
         out["ksize"] = np.array([p["ksize"] for p in ps], np.int32)
     if "sigma" in ps[0]:
         out["sigma"] = np.array([p["sigma"] for p in ps], np.float32)
+    if "bg" in ps[0]:
+        out["bg"] = np.array([p["bg"] for p in ps], np.int32)
+    if "sharpen_ks" in ps[0]:
+        out["sharpen_ks"] = np.array([p["sharpen_ks"] for p in ps], np.int32)
+        out["sharpen_mode"] = np.array([p["sharpen_mode"] for p in ps], np.int32)
+        out["sharpen_alpha"] = np.array([p["sharpen_alpha"] for p in ps], np.float64)
     return out
 
 
@@ -282,6 +352,40 @@ def filt(frames, ksize=None, sigma=None, gray=False, key=0):
     return out
 
 
+def background(frames, masks, pool, bg_index):
+    """In place on frames (masks are read).  pool: a BackgroundPool on the frames' device; bg_index (B,) host ints, -1 =
+    this image keeps its pixels, i = every mask == 0 pixel takes background i resized to the frame."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W, _ = frames.shape
+    idx = np.asarray(bg_index, np.int64).reshape(B)
+    if ((idx < -1) | (idx >= pool.n)).any():
+        raise ValueError("background index outside [-1, %d): %s" % (pool.n, idx.tolist()))
+    i = _dev(idx.astype(np.int32), torch.int32, frames.device)
+    check(lib.kd6d_aug_background(ops._ptr(frames), ops._ptr(masks), B, H, W, ops._ptr(pool.pool), pool.nbytes,
+                                  ops._ptr(pool.off), ops._ptr(pool.hw), pool.n, ops._ptr(i), ops._stream()),
+          "kd6d_aug_background")
+
+
+def sharpen(frames, ks, mode, alpha):
+    """-> new buffer.  ks (B,) host ints in {0, 5, 7, 9, 11} (0 = copy), mode (B,) (non-zero = ratio), alpha (B,)."""
+    from .. import ops
+    from ..ops import check, lib
+    B, H, W, _ = frames.shape
+    dev = frames.device
+    ks = np.asarray(ks, np.int32).reshape(B)
+    if not np.isin(ks, (0,) + SHARPEN_KS).all():
+        raise ValueError("sharpen box sizes must be 0 or one of %s (got %s)" % (SHARPEN_KS, ks.tolist()))
+    km = _dev(np.concatenate([ks, np.asarray(mode, np.int32).reshape(B)]), torch.int32, dev)
+    a = _dev(np.asarray(alpha, np.float64).reshape(B), torch.float64, dev)
+    nws = int(lib.kd6d_aug_sharpen_ws_bytes(B))
+    ws = torch.empty((nws + 7) // 8, dtype=torch.int64, device=dev)
+    out = torch.empty_like(frames)
+    check(lib.kd6d_aug_sharpen(ops._ptr(frames), ops._ptr(out), B, H, W, ops._ptr(km[:B]), ops._ptr(km[B:]), ops._ptr(a),
+                               ops._ptr(ws), ws.numel() * 8, ops._stream()), "kd6d_aug_sharpen")
+    return out
+
+
 def relabel(masks, lut):
     """In place.  lut (B, max_id + 1) host float32."""
     from .. import ops
@@ -293,12 +397,81 @@ def relabel(masks, lut):
           "kd6d_aug_relabel")
 
 
+def _probe_background(path):
+    """(h, w) of an image file from its header (Pillow opens lazily)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+    return int(h), int(w)
+
+
+def _decode_background(path):
+    """One background as the frames are: Pillow decode + BOP_Dataset's frame clean-up -> (h, w, 3) BGR uint8."""
+    from .dataset import load_image_cached, normalise_frame
+    img = load_image_cached(path, None)
+    if img is None:
+        raise ValueError("background image %s cannot be decoded" % path)
+    return np.ascontiguousarray(normalise_frame(img)[:, :, :3])
+
+
+class BackgroundPool:
+    """The backgrounds of RandomBackground on the device, decoded ONCE and kept at their native sizes in one packed
+    uint8 buffer (`pool`, BGR, image after image, no padding) with an (n, 2) int32 table of (h, w) (`hw`) and an (n,)
+    int64 table of byte offsets (`off`); kd6d_aug_background resizes while it samples.  Built once per process by
+    AugmentFront (under torch.distributed every rank holds its own).  A pool over budget_bytes is refused before
+    anything is decoded or allocated; a file that cannot be read is an error naming it (the reference draws another
+    file instead).  probe(path) -> (h, w) and decode(path) -> (h, w, 3) uint8 can be replaced (tests)."""
+
+    def __init__(self, directory, names, device, budget_bytes, probe=None, decode=None):
+        probe, decode = probe or _probe_background, decode or _decode_background
+        paths = [os.path.join(directory, n) for n in names]
+        hw, off, total = self.plan(paths, budget_bytes, probe)
+        buf = np.empty(total, np.uint8)
+        for p, (h, w), o in zip(paths, hw, off):
+            img = np.asarray(decode(p))
+            if img.shape != (h, w, 3) or img.dtype != np.uint8:
+                raise ValueError("background image %s decodes to %s %s, expected (%d, %d, 3) uint8"
+                                 % (p, img.shape, img.dtype, h, w))
+            buf[o:o + h * w * 3] = img.reshape(-1)
+        self.n, self.nbytes, self.names = len(paths), int(total), list(names)
+        self.hw_host, self.off_host = hw, off
+        self.pool = torch.from_numpy(buf).to(device)
+        self.hw = torch.from_numpy(hw).to(device)
+        self.off = torch.from_numpy(off).to(device)
+
+    @staticmethod
+    def plan(paths, budget_bytes, probe):
+        """-> ((n, 2) int32 sizes, (n,) int64 byte offsets, total bytes); raises when the total exceeds the budget."""
+        if not paths:
+            raise ValueError("a background pool needs at least one image")
+        hw = np.zeros((len(paths), 2), np.int32)
+        for i, p in enumerate(paths):
+            try:
+                h, w = probe(p)
+            except Exception as e:
+                raise ValueError("background image %s cannot be read: %s" % (p, e)) from e
+            if h < 1 or w < 1:
+                raise ValueError("background image %s has size %dx%d" % (p, w, h))
+            hw[i] = (h, w)
+        sizes = hw[:, 0].astype(np.int64) * hw[:, 1].astype(np.int64) * 3
+        off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        total = int(sizes.sum())
+        if total > int(budget_bytes):
+            raise ValueError("the %d background images need %d bytes of device memory, over the budget of %d bytes: "
+                             "raise --aug_background_gb" % (len(paths), total, int(budget_bytes)))
+        return hw, off, total
+
+
 class AugmentFront:
     """The GPU half of --augment, run by DziLoader on each training batch."""
 
     def __init__(self, ac, device):
         self.ac, self.device = ac, device
         self._box = None                     # (host copy, device copy) of the last box table kd6d_pose_remap read
+        self.pool = None
+        if ac.background_on:
+            self.pool = BackgroundPool(ac.background_dir, ac.background_files, device,
+                                       int(ac.background_gb * 2 ** 30))
 
     def _box_table(self, targets):
         """The (n_class, 8, 3) box corners the batch's class ids index, on the device (uploaded when they change).
@@ -379,6 +552,11 @@ class AugmentFront:
             cur, cur_m = cur.clone(), cur_m.clone()          # the resized frame is kept for the fallback
             st = mask_stats(cur_m, max(max_id, MAX_GT))
             occlude(cur, cur_m, st, params["occl_u"], n_inst, ac.occlusion, key)
+        # 2b RandomBackground (--aug_chain full): mask == 0 pixels of the images that drew one; no launch otherwise
+        if ac.background_on and (np.asarray(params["bg"]) >= 0).any():
+            if cur is resized:
+                cur = cur.clone()                                # the resized frame is kept for the fallback
+            background(cur, cur_m, self.pool, params["bg"])
         # 3 RandomShiftScaleRotate
         if ac.ssr_on:
             cur, cur_m = warp(cur, cur_m, params["M_ssr"], size)
@@ -387,6 +565,9 @@ class AugmentFront:
             if cur is resized:
                 cur = cur.clone()
             hsv(cur, params["hsv"])
+        # 4b RandomPencilSharpen (--aug_chain full): a new buffer; no launch when no image of the batch drew it
+        if ac.sharpen_on and (np.asarray(params["sharpen_ks"]) > 0).any():
+            cur = sharpen(cur, params["sharpen_ks"], params["sharpen_mode"], params["sharpen_alpha"])
         # 5-7 RandomSmooth, RandomNoise, Grayscalize
         if ac.smooth_on or ac.noise_on or ac.gray:
             cur = filt(cur, params.get("ksize"), params.get("sigma"), ac.gray, key)
