@@ -222,6 +222,26 @@ int kd6d_conv2d_wgrad_parts(const kd6d_conv_geom* g, int dtype, int with_bias, i
 int kd6d_conv2d_wgrad(const kd6d_conv_geom* g, int dtype, const void* x, const void* dy, float* dw_slab,
                       int64_t slab_floats, int64_t* dbias_acc, int64_t acc_hi_stride, int cu_budget, void* stream);
 
+/* Several weight gradients behind ONE point of the caller's stream: every call is exactly a kd6d_conv2d_wgrad call (same
+ * arguments, same checks, same plan for its cu_budget, same parts, same bits in its slab and bias accumulators).  The
+ * bf16 calls of the transposing kernel family go out as list launches of up to KD6D_WGRAD_LIST_MAX calls each -- one
+ * kernel whose workgroups are the calls' own grids back to back, so the calls run side by side without a stream each;
+ * n may exceed KD6D_WGRAD_LIST_MAX: consecutive lists, call order kept.  A call the list kernel does not take (the
+ * narrow-layer family, fp32) is launched on its own directly behind the list that reached it. */
+#define KD6D_WGRAD_LIST_MAX 4
+typedef struct kd6d_wgrad_call {
+  const kd6d_conv_geom* g;
+  int dtype;
+  const void* x;
+  const void* dy;
+  float* dw_slab;
+  int64_t slab_floats;
+  int64_t* dbias_acc;
+  int64_t acc_hi_stride;
+  int cu_budget;
+} kd6d_wgrad_call;
+int kd6d_conv2d_wgrad_list(const kd6d_wgrad_call* calls, int n, void* stream);
+
 /* wt[cin][ky][kx][cout] <- w[cout][ky][kx][cin] for n_layers layers in one
  * launch.  desc_dev: int32[n_layers*6] = {w_off, wt_off, cout, cin, ksize,
  * first_block}; offsets in elements of the w / wt base arrays. */
@@ -290,6 +310,9 @@ int kd6d_device_cu_count(void);
  *   sinkhorn.dense_rows  rows per workgroup of the dense matrix-pipe softmins (each workgroup streams all columns through
  *                  LDS): -1 = 128 from 8192 rows up, 64 below | 64 | 128
  *   stem.fused      1 | 0 kd6d_bn_pool_bwd_wgrad_parts reports 0: the apply pass and the weight gradient stay two launches
+ *   wgrad.list      the largest number of per-layer weight gradients a reverse sweep collects before it forks them onto a
+ *                  side stream as one kd6d_conv2d_wgrad_list call; 0 or 1: a fork per layer (read by the caller's sweep,
+ *                  kd6d/engine.py; the library's launches do not depend on it)
  * Unknown names return KD6D_ERR_ARG. */
 /* Context: the library's mutable state -- the option table, the pair bracket of kd6d_conv2d_pair_begin/_end and the
  * counter of in-kernel barrier waits that gave up -- lives in a kd6d_ctx.  Every entry point of this header acts on the

@@ -18,6 +18,8 @@
 //   bf16: v_mfma_f32_16x16x32_bf16, one granule per lane per 32-deep chunk.
 //   fp32: v_mfma_f32_16x16x4_f32 x8 on a 32-deep chunk; lane group q holds
 //         k = 8q..8q+7 (two granules) and MFMA j contracts {8q+j}: exact fp32.
+#include <vector>
+
 #include "conv_common.h"
 
 using namespace kd6d_detail;
@@ -903,8 +905,10 @@ __device__ __forceinline__ bf16x8_t tr_frag(const char* tile, int cb, int kc, in
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
+// The body is shared by the per-layer launch (conv_wgrad_tr_kernel) and the list launch (conv_wgrad_tr_list_kernel):
+// block_x / block_y are the workgroup's coordinates inside the layer's OWN grid (plan_wgrad), smem the launch's dynamic LDS.
 template <int BN, int WN, int WJ>
-__global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradParams p) {
+__device__ __forceinline__ void conv_wgrad_tr_body(const WgradParams& p, const int block_x, const int block_y, char* smem) {
   constexpr int BJ = 128, BKM = 64;
   constexpr int NI = BN / WN / 16;
   constexpr int JI = BJ / WJ / 16;
@@ -914,19 +918,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradParams p)
   constexpr int EP = BJ + 4;                // fp32 pitch of the epilogue image
   static_assert(WN * WJ == 4 && NI >= 1 && JI >= 1, "4 waves");
 
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int wn = wave % WN;
   const int wj = wave / WN;
 
-  const int tile_j = blockIdx.x % p.n_jtiles;
-  const int tile_n = blockIdx.x / p.n_jtiles;
+  const int tile_j = block_x % p.n_jtiles;
+  const int tile_n = block_x / p.n_jtiles;
   const int n0 = tile_n * BN;
   const int j0 = tile_j * BJ;
-  const int m_lo = blockIdx.y * p.m_chunk;
+  const int m_lo = block_y * p.m_chunk;
   int m_hi = m_lo + p.m_chunk;
   if (m_hi > p.M) m_hi = p.M;
   const int nsteps = (m_hi - m_lo + BKM - 1) / BKM;
@@ -1084,7 +1086,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradParams p)
       for (int r = 0; r < 4; ++r) et[(nl + r) * EP + jl] = acc[a][b][r];
     }
   __syncthreads();
-  float* part = p.dw + (size_t)blockIdx.y * (size_t)p.Cout * (size_t)p.J;      // this split's partial image
+  float* part = p.dw + (size_t)block_y * (size_t)p.Cout * (size_t)p.J;      // this split's partial image
   for (int nl = wave; nl < BN; nl += 4) {
     const int n = n0 + nl;
     if (n >= p.Cout) break;
@@ -1094,6 +1096,50 @@ __global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradParams p)
       const int j = j0 + jl;
       if (j < p.J) part[(size_t)n * (size_t)p.J + (size_t)j] = et[nl * EP + jl];
     }
+  }
+}
+
+template <int BN, int WN, int WJ>
+__global__ __launch_bounds__(256) void conv_wgrad_tr_kernel(const WgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  conv_wgrad_tr_body<BN, WN, WJ>(p, blockIdx.x, blockIdx.y, smem);
+}
+
+// Several layers' weight gradients as ONE launch: the workgroups of up to KD6D_WGRAD_LIST_MAX per-layer grids back to back.
+// Entry e owns the workgroups first_block[e] ... first_block[e + 1] - 1 and runs, in each of them, exactly what workgroup
+// (block_x, block_y) of its own conv_wgrad_tr_kernel launch runs: the same tiles, pixel splits and k-step order, hence the
+// same bits in its slab and bias accumulators.  The list travels BY VALUE as the kernel argument (a captured graph node
+// carries it; nothing lives in device memory).  No workgroup waits for another.
+struct WgradListEntry {
+  WgradParams p;
+  int variant;          // the entry's tile of KD6D_CONV_WGRAD_TR_TILES, named by its BN
+  int grid_x, grid_y;   // the entry's own grid
+  int first_block;      // prefix sum of grid_x * grid_y
+};
+struct WgradList {
+  int n;
+  WgradListEntry e[KD6D_WGRAD_LIST_MAX];
+};
+static_assert(KD6D_WGRAD_LIST_MAX == kd6d_conv::kWgradListMax, "conv_plan.h restates KD6D_WGRAD_LIST_MAX");
+static_assert(sizeof(WgradList) == kd6d_conv::kWgradListBytes && sizeof(WgradList) == 1288 && sizeof(WgradList) < 4096,
+              "the list is one kernel argument of 1288 bytes: under the 4-KB limit");
+
+__global__ __launch_bounds__(256) void conv_wgrad_tr_list_kernel(const WgradList L) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int e = 0;
+#pragma unroll
+  for (int i = 1; i < KD6D_WGRAD_LIST_MAX; ++i)
+    if (i < L.n && (int)blockIdx.x >= L.e[i].first_block) e = i;
+  const WgradListEntry& q = L.e[e];
+  const int local = (int)blockIdx.x - q.first_block;
+  const int block_y = local / q.grid_x;
+  const int block_x = local - block_y * q.grid_x;
+  switch (q.variant) {
+#define KD6D_CASE(bn, wn, wj) \
+    case bn: conv_wgrad_tr_body<bn, wn, wj>(q.p, block_x, block_y, smem); break;
+    KD6D_CONV_WGRAD_TR_TILES(KD6D_CASE)
+#undef KD6D_CASE
+    default: break;
   }
 }
 
@@ -1628,23 +1674,34 @@ extern "C" int kd6d_conv2d_wgrad_parts(const kd6d_conv_geom* g, int dtype, int w
   return parts;
 }
 
+namespace {
+// one call of kd6d_conv2d_wgrad / kd6d_conv2d_wgrad_list checked and planned; launches nothing
+int wgrad_prepare(const kd6d_wgrad_call& c, const char* who, WgradParams& p, WgradPlan& pl) {
+  KD6D_CHECK_ARG(c.g != nullptr, "%s: null geometry", who);
+  int rc = wgrad_params(c.g, c.dtype, c.cu_budget, who, p);
+  if (rc) return rc;
+  KD6D_CHECK_ARG(c.x && c.dy && c.dw_slab, "%s: null tensor pointer", who);
+  KD6D_CHECK_ARG(!c.dbias_acc || c.acc_hi_stride != 0, "%s: acc_hi_stride = 0 with a bias accumulator", who);
+  p.x = c.x; p.dy = c.dy;
+  p.dw = c.dw_slab; p.slab_floats = (long long)c.slab_floats;
+  p.dbias = reinterpret_cast<long long*>(c.dbias_acc); p.acc_hi = (long long)c.acc_hi_stride;
+  pl = wgrad_plan(p, c.g, c.dtype, c.dbias_acc != nullptr);
+  KD6D_CHECK_ARG((long long)pl.parts * p.Cout * p.J <= p.slab_floats,
+                 "%s: slab of %lld floats is too small (kd6d_conv2d_wgrad_parts x cout*k*k*cin)", who,
+                 (long long)c.slab_floats);
+  return KD6D_OK;
+}
+}  // namespace
+
 extern "C" int kd6d_conv2d_wgrad(const kd6d_conv_geom* g, int dtype, const void* x, const void* dy,
                                  float* dw_slab, int64_t slab_floats, int64_t* dbias, int64_t acc_hi_stride,
                                  int cu_budget, void* stream) {
+  const kd6d_wgrad_call c = {g, dtype, x, dy, dw_slab, slab_floats, dbias, acc_hi_stride, cu_budget};
   WgradParams p;
-  int rc = wgrad_params(g, dtype, cu_budget, "kd6d_conv2d_wgrad", p);
+  WgradPlan pl;
+  int rc = wgrad_prepare(c, "kd6d_conv2d_wgrad", p, pl);
   if (rc) return rc;
-  KD6D_CHECK_ARG(x && dy && dw_slab, "kd6d_conv2d_wgrad: null tensor pointer");
-  KD6D_CHECK_ARG(!dbias || acc_hi_stride != 0, "kd6d_conv2d_wgrad: acc_hi_stride = 0 with a bias accumulator");
-  p.x = x; p.dy = dy;
-  p.dw = dw_slab; p.slab_floats = (long long)slab_floats;
-  p.dbias = reinterpret_cast<long long*>(dbias); p.acc_hi = (long long)acc_hi_stride;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const WgradPlan pl = wgrad_plan(p, g, dtype, dbias != nullptr);
-  KD6D_CHECK_ARG((long long)pl.parts * p.Cout * p.J <= p.slab_floats,
-                 "kd6d_conv2d_wgrad: slab of %lld floats is too small (kd6d_conv2d_wgrad_parts x cout*k*k*cin)",
-                 (long long)slab_floats);
-  if (!launch_wgrad(pl, p, st)) {
+  if (!launch_wgrad(pl, p, reinterpret_cast<hipStream_t>(stream))) {
     kd6d_set_error("kd6d_conv2d_wgrad: no kernel is built for the planned variant (family %d)", pl.family);
     return KD6D_ERR_UNSUPPORTED;
   }
@@ -1653,6 +1710,55 @@ extern "C" int kd6d_conv2d_wgrad(const kd6d_conv_geom* g, int dtype, const void*
     if (rc) return rc;
   }
   KD6D_CHECK_LAUNCH("kd6d_conv2d_wgrad");
+  return KD6D_OK;
+}
+
+extern "C" int kd6d_conv2d_wgrad_list(const kd6d_wgrad_call* calls, int n, void* stream) {
+  const char* who = "kd6d_conv2d_wgrad_list";
+  KD6D_CHECK_ARG(calls != nullptr && n >= 1, "%s: no calls", who);
+  std::vector<WgradParams> params((size_t)n);
+  std::vector<WgradPlan> plans((size_t)n);
+  for (int i = 0; i < n; ++i) {      // every check before the first launch
+    int rc = wgrad_prepare(calls[i], who, params[(size_t)i], plans[(size_t)i]);
+    if (rc) return rc;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int begin = 0; begin < n;) {
+    const kd6d_conv::WgradListPlan lp = kd6d_conv::plan_wgrad_list(plans.data(), n, begin);
+    if (lp.n == 1) {                 // a list of one is the call's own launch
+      if (!launch_wgrad(plans[(size_t)lp.call[0]], params[(size_t)lp.call[0]], st)) {
+        kd6d_set_error("%s: no kernel is built for the planned variant", who);
+        return KD6D_ERR_UNSUPPORTED;
+      }
+    } else if (lp.n > 1) {
+      WgradList L;
+      memset(&L, 0, sizeof(L));
+      L.n = lp.n;
+      for (int e = 0; e < lp.n; ++e) {
+        const WgradPlan& pl = plans[(size_t)lp.call[e]];
+        L.e[e].p = params[(size_t)lp.call[e]];
+        L.e[e].p.n_jtiles = pl.n_jtiles; L.e[e].p.m_chunk = pl.m_chunk;
+        L.e[e].variant = lp.variant[e];
+        L.e[e].grid_x = lp.grid_x[e]; L.e[e].grid_y = lp.grid_y[e];
+        L.e[e].first_block = lp.first_block[e];
+      }
+      launch_kernel<conv_wgrad_tr_list_kernel>(dim3(lp.grid), 256, lp.lds_bytes, st, L);
+    }
+    for (int i = begin; i < lp.end; ++i) {       // what the list kernel does not take: on its own, behind the list
+      if (kd6d_conv::wgrad_listable(plans[(size_t)i])) continue;
+      if (!launch_wgrad(plans[(size_t)i], params[(size_t)i], st)) {
+        kd6d_set_error("%s: no kernel is built for the planned variant (family %d)", who, plans[(size_t)i].family);
+        return KD6D_ERR_UNSUPPORTED;
+      }
+      if (calls[i].dtype != KD6D_BF16 && calls[i].dbias_acc) {
+        int rc = kd6d_detail::colsum_grad_planar(calls[i].dtype, calls[i].dy, params[(size_t)i].M, calls[i].g->cout,
+                                                 params[(size_t)i].dbias, params[(size_t)i].acc_hi, stream);
+        if (rc) return rc;
+      }
+    }
+    begin = lp.end;
+  }
+  KD6D_CHECK_LAUNCH(who);
   return KD6D_OK;
 }
 

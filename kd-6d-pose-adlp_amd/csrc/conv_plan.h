@@ -605,5 +605,65 @@ inline WgradPlan plan_wgrad(const Shape& p, const Flags& f, const Options& o, in
   return pl;
 }
 
+// ---- list launch of the transposing weight gradient (conv_wgrad_tr_list_kernel) ---------------------------------
+// Up to kWgradListMax per-layer weight gradients as ONE launch: entry e keeps the grid plan_wgrad gave its call (same
+// cu_budget, same tiles, same pixel splits) and owns the workgroups first_block[e] ... first_block[e + 1] - 1 of the list's
+// one-dimensional grid, row-major over its own (grid_x, grid_y).  Listable: what plan_wgrad sends to the transposing
+// family (bf16, not the narrow-layer kernel).  kWgradListBytes: sizeof of the kernel's by-value argument (conv_igemm.hip
+// asserts it), under the 4-KB kernel-argument limit.
+constexpr int kWgradListMax = 4;
+constexpr int kWgradListBytes = 1288;
+constexpr int kKernargLimit = 4096;
+static_assert(kWgradListBytes < kKernargLimit, "the list is passed by value");
+
+struct WgradListPlan {
+  int n = 0;                               // entries of this list (0: no listable call in [begin, end))
+  int end = 0;                             // the next list starts at this call
+  int call[kWgradListMax] = {0, 0, 0, 0};  // which call an entry stands for, in call order
+  int variant[kWgradListMax] = {0, 0, 0, 0};       // its tile of KD6D_CONV_WGRAD_TR_TILES, named by BN
+  int grid_x[kWgradListMax] = {0, 0, 0, 0}, grid_y[kWgradListMax] = {0, 0, 0, 0};
+  int first_block[kWgradListMax + 1] = {0, 0, 0, 0, 0};
+  int grid = 0;                            // workgroups of the launch = first_block[n]
+  long long lds_bytes = 0;                 // the largest entry's
+};
+
+inline bool wgrad_listable(const WgradPlan& pl) {
+  if (pl.family != kWgTr) return false;
+#define KD6D_CONV_LISTED(bn, wn, wj) if (pl.BN == bn && pl.WN == wn && pl.WJ == wj) return true;
+  KD6D_CONV_WGRAD_TR_TILES(KD6D_CONV_LISTED)
+#undef KD6D_CONV_LISTED
+  return false;
+}
+
+// The list that starts at call `begin` of plans[0 .. n_calls): the next (at most kWgradListMax) listable calls in call
+// order.  Calls of [begin, end) that are not listable get no slot: the caller launches each on its own behind the list.
+inline WgradListPlan plan_wgrad_list(const WgradPlan* plans, int n_calls, int begin) {
+  WgradListPlan L;
+  int i = begin;
+  for (; i < n_calls && L.n < kWgradListMax; ++i) {
+    const WgradPlan& pl = plans[i];
+    if (!wgrad_listable(pl)) continue;
+    const int e = L.n++;
+    L.call[e] = i; L.variant[e] = pl.BN;
+    L.grid_x[e] = pl.grid_x; L.grid_y[e] = pl.grid_y;
+    L.first_block[e + 1] = L.first_block[e] + pl.grid_x * pl.grid_y;
+    if (pl.lds_bytes > L.lds_bytes) L.lds_bytes = pl.lds_bytes;
+  }
+  // (a list that filled up ends right behind its last entry: what follows belongs to the next list)
+  L.end = i;
+  L.grid = L.first_block[L.n];
+  return L;
+}
+
+// which (entry, block_x, block_y) workgroup `block` of the list's grid is: the kernel's own decode
+inline void wgrad_list_decode(const WgradListPlan& L, int block, int& entry, int& block_x, int& block_y) {
+  entry = 0;
+  for (int i = 1; i < L.n; ++i)
+    if (block >= L.first_block[i]) entry = i;
+  const int local = block - L.first_block[entry];
+  block_y = local / L.grid_x[entry];
+  block_x = local - block_y * L.grid_x[entry];
+}
+
 }  // namespace kd6d_conv
 #endif  // KD6D_CONV_PLAN_H_

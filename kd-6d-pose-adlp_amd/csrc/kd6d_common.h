@@ -59,6 +59,7 @@ enum Kd6dOption {
                                    // difference form | 0 every pair in the difference form
   KD6D_OPT_SINKHORN_DENSE_ROWS,    // rows per workgroup of the dense matrix-pipe softmins: -1 = 128 from 8192 rows up, else 64 | 64 | 128
   KD6D_OPT_STEM_FUSED,             // 1 | 0: kd6d_bn_pool_bwd_wgrad_parts reports 0 (apply pass + weight gradient stay two launches)
+  KD6D_OPT_WGRAD_LIST,             // per-layer weight gradients collected before one fork (0 / 1: a fork per layer); read by the caller
   KD6D_OPT_COUNT
 };
 long long kd6d_opt(int id);          // of the calling thread's current context

@@ -47,6 +47,13 @@ class WgradItem(ctypes.Structure):
                 ("dbias", ctypes.c_void_p)]
 
 
+class WgradCall(ctypes.Structure):
+    """kd6d_wgrad_call: the arguments of one kd6d_conv2d_wgrad call."""
+    _fields_ = [("g", ctypes.POINTER(ConvGeom)), ("dtype", ctypes.c_int), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p),
+                ("dw_slab", ctypes.c_void_p), ("slab_floats", ctypes.c_int64), ("dbias_acc", ctypes.c_void_p),
+                ("acc_hi_stride", ctypes.c_int64), ("cu_budget", ctypes.c_int)]
+
+
 class ConvNorm(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("groups", ctypes.c_int32), ("act", ctypes.c_int32), ("eps", ctypes.c_float),
                 ("momentum", ctypes.c_float)] + [(n, ctypes.c_void_p) for n in (
@@ -111,6 +118,7 @@ SIGNATURES = {
     "kd6d_conv2d_dgrad": [_G, _I, _P, _P, _P, _I, _P],
     "kd6d_conv2d_wgrad": [_G, _I, _P, _P, _P, _I64, _P, _I64, _I, _P],
     "kd6d_conv2d_wgrad_parts": [_G, _I, _I, _I],
+    "kd6d_conv2d_wgrad_list": [ctypes.POINTER(WgradCall), _I, _P],
     "kd6d_acc_read": [_P, _I64, _I, _P, _I, _I, _P],
     "kd6d_grad_acc_resolve": [_P, _I, _I, _P, _I64, _P, _P],
     "kd6d_grad_acc_resolve_part_groups": [_I],

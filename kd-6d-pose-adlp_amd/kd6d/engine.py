@@ -315,6 +315,17 @@ class Conv:
             # per-layer buffers that stay untouched until the sweep has joined its side streams
             grp.add(g, x, dy, st.storage(self.w, "grads"), None if self.b is None else st.storage(self.b, "grads"),
                     flops=self.flops(g))
+        elif (limit := self.net.wgrad_list_limit()) > 1:
+            # collected: the sweep forks once for several layers and their weight gradients go out as ONE list launch
+            # (PoseNet.flush_wgrad_list).  x is a tensor of the forward tape and dy this layer's own gradient buffer
+            # (draw / d_inner / a slice of d_head_in): the sweep writes neither again, so the later launch reads what
+            # this one would have read
+            budget = self.net.wgrad_budget()
+            self.net._wgrad_pending.append(dict(
+                geom=g, x=x, dy=dy, dw_slab=self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
+                dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride, cu_budget=budget))
+            if len(self.net._wgrad_pending) >= limit:
+                self.net.flush_wgrad_list()
         elif (side := self.net.next_side_stream()) is None:
             budget = self.net.wgrad_budget()         # (0: the device)
             ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
@@ -594,6 +605,11 @@ class PoseNet:
         # cls / pose tower layers as one launch (training): 0 = off, 1 = forward and data gradients, 2 = forward only
         self.pair_towers = 1
         self._side_rr = 0
+        # per-layer weight gradients waiting for their fork (Conv.bwd, option wgrad.list); wgrad_list_tail: the sweep is
+        # inside its last blocks, where every layer forks at once again (a list launched behind the last chain kernel
+        # would run alone)
+        self._wgrad_pending = []
+        self.wgrad_list_tail = False
         feat, oc = BACKBONE_CFG[arch]
         self.out_channel = oc
         self.n_levels = 5 if arch == "darknet53" else 4
@@ -757,6 +773,28 @@ class PoseNet:
             self._side_rr = (self._side_rr + 1) % len(self.side_streams)
             return self.side_streams[self._side_rr]
         return self.side_stream
+
+    WGRAD_LIST_TAIL_BLOCKS = 2      # blocks at the end of the backbone sweep whose weight gradients fork per layer
+
+    def wgrad_list_limit(self):
+        """How many per-layer weight gradients Conv.bwd collects before one fork (option wgrad.list); 0: a fork per layer
+        -- no side stream to fork onto, the option off, or the end of the sweep."""
+        if self.wgrad_list_tail or not (self.side_streams or self.side_stream is not None):
+            return 0
+        n = ops.get_option("wgrad.list")
+        return n if n > 1 else 0
+
+    def flush_wgrad_list(self):
+        """One fork for the collected per-layer weight gradients: one wait_stream, one side stream, one
+        ops.conv2d_wgrad_list (the transposing-family calls side by side inside list launches)."""
+        calls = self._wgrad_pending
+        if not calls:
+            return
+        self._wgrad_pending = []
+        side = self.next_side_stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            ops.conv2d_wgrad_list(calls)
 
     def flush_wgrad_group(self):
         """Launch the collected weight gradients (on a side stream when there is one: nothing in the sweep reads dW)."""
@@ -1034,6 +1072,7 @@ class PoseNet:
         if self.use_wgrad_group and self.dtype == torch.bfloat16 and self.wgrad_group is None:
             self.wgrad_group = ops.WgradGroup(self.wgrad_group_wgs or max(ops.device_cu_count() // 2, 1))
         self.grouping = self.wgrad_group is not None
+        self._wgrad_pending, self.wgrad_list_tail = [], False
         d_head_in = self.buf("d_head_in", (r, oc))
         first = True
         towers = (("cls", self.cls_tower, self.cls_logits, dcls), ("pose", self.pose_tower, self.pose_pred, dreg))
@@ -1135,11 +1174,14 @@ class PoseNet:
         if self.grad_hook is not None:
             # every gradient outside the backbone has been issued (on this stream or on the weight-gradient streams):
             # a data-parallel caller starts their exchange here, beside the backbone sweep
+            self.flush_wgrad_list()
             self.grad_hook()
         if self.arch == "darknet53":
             self._backbone53_bwd(dfeat)
         else:
             self._backbone_tiny_bwd(dfeat[top], dfeat.get(2))
+        self.wgrad_list_tail = False
+        self.flush_wgrad_list()              # (what a sweep shorter than the tail rule left)
         ops.mark("student.bwd.main.end")
         for side in (self.side_streams or ([self.side_stream] if self.side_stream is not None else [])):
             torch.cuda.current_stream().wait_stream(side)
@@ -1149,14 +1191,28 @@ class PoseNet:
         self.store.resolve_grads(0, self.resolve_hi)
         return None
 
+    def _wgrad_tail_start(self):
+        """Tape index at which the reverse sweep enters its last WGRAD_LIST_TAIL_BLOCKS blocks (a unit counts as one)."""
+        blocks = [i for i, rec in enumerate(self.tape) if rec[0] not in ("stage", "pool", "pooled")]
+        n = min(self.WGRAD_LIST_TAIL_BLOCKS, len(blocks))
+        return blocks[n - 1] if n else -1
+
+    def _enter_wgrad_tail(self):
+        # the lists collected so far go out now, beside the chain kernels still to come; from here on a fork per layer
+        self.flush_wgrad_list()
+        self.wgrad_list_tail = True
+
     def _backbone53_bwd(self, dfeat):
         """Reverse sweep of Darknet-53's backbone over the training tape.  dfeat: stage index (2, 3, 4) -> the FPN's
         gradient of that stage's output; the stage-3 / stage-4 ones are added by the data gradient of the next stage's
         down-sampling block (accumulate=True into the FPN's buffer)."""
         tape = self.tape
         grad = dfeat[len(self.stages) - 1]
+        tail_at = self._wgrad_tail_start()
         for i_rec in range(len(tape) - 1, -1, -1):
             rec = tape[i_rec]
+            if i_rec == tail_at:
+                self._enter_wgrad_tail()
             if rec[0] == "stage":
                 continue
             if rec[0] == "unit":
@@ -1181,8 +1237,11 @@ class PoseNet:
         i_rec = len(self.tape) - 1
         pools_seen = 0
         n_pools = sum(1 for t in self.tape if t[0] == "pool")
+        tail_at = self._wgrad_tail_start()
         while i_rec >= 0:
             rec = self.tape[i_rec]
+            if i_rec == tail_at:
+                self._enter_wgrad_tail()
             if rec[0] == "pooled":              # the pool lives inside the block's BN kernels; out3 = after pool 2
                 if rec[1] == 2 and pending[2] is not None:
                     grad = ops.eltwise(ops.ELT_ADD, grad, pending[2], self.buf("d_out3", grad.shape))

@@ -269,6 +269,32 @@ def conv2d_wgrad(geom, x, dy, dw_slab, flops=0, dbias=None, acc_stride=0, cu_bud
     return dw_slab
 
 
+def conv2d_wgrad_list(calls):
+    """Several conv2d_wgrad calls behind one point of the current stream (kd6d_conv2d_wgrad_list): the bf16 calls of the
+    transposing kernel family as list launches of up to four, side by side inside one kernel; every slab and bias
+    accumulator gets the bits its own conv2d_wgrad call gives.  calls: dicts with conv2d_wgrad's arguments (geom, x, dy,
+    dw_slab, flops, dbias, acc_stride, cu_budget).  While per-launch events are recorded (the instrumented eager steps)
+    the calls go out one by one, so that every layer keeps its own entry."""
+    if _prof is not None or len(calls) == 1:
+        for c in calls:
+            conv2d_wgrad(c["geom"], c["x"], c["dy"], c["dw_slab"], flops=c.get("flops", 0), dbias=c.get("dbias"),
+                         acc_stride=c.get("acc_stride", 0), cu_budget=c.get("cu_budget", 0))
+        return
+    arr = (_lib.WgradCall * len(calls))()
+    for a, c in zip(arr, calls):
+        geom, x, dy, slab, dbias = c["geom"], c["x"], c["dy"], c["dw_slab"], c.get("dbias")
+        acc_stride = c.get("acc_stride", 0)
+        assert x.shape == (geom.rows_in, geom.cin) and dy.shape == (geom.rows_out, geom.cout)
+        assert x.dtype == dy.dtype and slab.dtype == torch.float32 and slab.is_contiguous()
+        assert slab.numel() % (geom.cout * geom.ksize * geom.ksize * geom.cin) == 0
+        assert dbias is None or (dbias.dtype == torch.int64 and dbias.numel() >= geom.cout and acc_stride > 0)
+        a.g, a.dtype = ctypes.pointer(geom.c), dt_code(x.dtype)
+        a.x, a.dy, a.dw_slab, a.slab_floats = _ptr(x).value, _ptr(dy).value, _ptr(slab).value, slab.numel()
+        a.dbias_acc = None if dbias is None else _ptr(dbias).value
+        a.acc_hi_stride, a.cu_budget = int(acc_stride), int(c.get("cu_budget", 0))
+    check(lib.kd6d_conv2d_wgrad_list(arr, len(calls), _stream()), "kd6d_conv2d_wgrad_list")
+
+
 def conv2d_wgrad_f32(geom, x, dy, with_bias=False, cu_budget=0):
     """Stand-alone weight gradient -> fp32 tensors (dw, dbias | None): slab and bias accumulators made, filled and
     reduced here (torch arithmetic on the device: tests and tools; the engine resolves with kd6d_grad_acc_resolve).
