@@ -770,8 +770,9 @@ int kd6d_kd_scatter_objects(const int32_t* pos_cnt, const int32_t* pos_gt, const
  * against y (M,D) with beta (M), D in {2,4,8,16}; cost matrices are never materialised (online logsumexp over
  * LDS-staged column tiles).  `diameter` > 0 is the box diagonal of all points (geomloss' diameter= argument);
  * kd6d_sinkhorn_dense_diameter computes it on the device (scratch64: 64 floats).  workspace:
- * kd6d_sinkhorn_dense_workspace_floats(N, M, D) floats, any contents.  Outputs: loss (1), grad_x (N,D),
- * grad_alpha (N). */
+ * kd6d_sinkhorn_dense_workspace_floats(N, M, D) floats, any contents (its regions and their sum are
+ * csrc/sinkhorn_plan.h's DenseWorkspace, as are the epsilon schedule and the kernel, rows and grid of every softmin
+ * launch).  Outputs: loss (1), grad_x (N,D), grad_alpha (N). */
 int64_t kd6d_sinkhorn_dense_workspace_floats(int N, int M, int D);
 int kd6d_sinkhorn_dense_diameter(const float* x, const float* y, int N, int M, int D, float* scratch64,
                                  float* diam_out, void* stream);

@@ -19,19 +19,20 @@
 #include <math.h>
 
 #include "kd6d_common.h"
+#include "sinkhorn_plan.h"
 
 namespace {
 
-constexpr int kThreadsD = 512;    // 2 waves per SIMD: a lone wave issues one VALU op per 4+ clk
-constexpr int kRows = 256;        // rows per workgroup of the default form: kSplit = 2 threads per row, each takes its share
-constexpr int kSplit = 2;         // of every column tile, merged at the end; the gradient form of the last extrapolation
+using namespace kd6d_sinkhorn;    // kThreadsD, kRows, kMRows, kSplitBytes, kYtBytes, kCenterWgs: shared with the launch rules
+
+constexpr int kSplit = 2;         // threads per row of the default form (kRows rows per workgroup): each takes its share
+                                  // of every column tile, merged at the end; the gradient form of the last extrapolation
                                   // runs on two of the four softmins only and takes SPLIT = 4 (128 rows per workgroup) so
                                   // that it still yields one workgroup per CU at N = 16384
 constexpr int kTile = 128;        // columns staged per LDS tile (kTile / kSplit per thread)
 constexpr float kNegLogD = -100000.f;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
-constexpr double kMfmaEpsRel = 1.5e-4;   // eps / diameter^2 from which the matrix-pipe softmin is taken (measured: tests)
 
 struct DenseArgs {
   const float* x; const float* y;          // (N,D), (M,D)
@@ -215,9 +216,7 @@ __global__ __launch_bounds__(kThreadsD) void dense_softmin_kernel(const DenseArg
 // below the fp32 noise the difference form has anyway (eps >= kMfmaEpsRel * diameter^2; the last, gradient-carrying
 // extrapolation and the small-eps steps keep the difference form above).
 // ---------------------------------------------------------------------------
-constexpr int kMRows = 64;         // rows per workgroup: 2 row groups of 32; the other two waves take the other column half
 constexpr int kMTile = 128;        // columns per LDS tile: 4 blocks of 32, two per wave
-constexpr int kSplitBytes = 96;    // prepared point: 3 pieces x 2 k-halves x 8 bf16
 constexpr int kMPitchB = 112;      // LDS bytes per column: 96 used; 28 dwords -> conflict-free ds_read_b128 over 16 columns
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
@@ -231,7 +230,6 @@ __device__ __forceinline__ void split3(float v, bf16_t& h, bf16_t& m, bf16_t& l)
 
 typedef _Float16 f16_t;
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-constexpr int kYtBytes = 64;            // per point: 16 dimensions x (hi, lo) fp16
 constexpr float kLoScale = 2048.f;      // the lo pieces travel scaled by 2^11 (kept out of fp16's subnormal range)
 
 // centred points -> MFMA-ready pieces [point][piece h,m,l][k half][8 bf16] + |p - centre|^2, once per call.
@@ -937,7 +935,6 @@ __global__ __launch_bounds__(256) void dense_softmin_mfma_grad_kernel(const Dens
 // then one small workgroup adds them up: the centre cancels mathematically, but its last bits decide how every point
 // splits into pieces, and at blur 0.001 the gradient turns a 1e-7 difference there into 2e-3 (float atomics made two
 // runs on the same inputs differ by that much).  (As ONE workgroup the whole reduction took 0.34 ms of a 5.3-ms image.)
-constexpr int kCenterWgs = 64;
 __global__ __launch_bounds__(256) void dense_center_kernel(const float* __restrict__ p, long long n_floats, int D,
                                                            float* __restrict__ partials) {
   __shared__ float part[256];
@@ -1044,142 +1041,105 @@ __global__ void dense_diam_kernel(const float* mn, const float* mx, int D, float
   }
 }
 
+// the one softmin dispatch: path and gradient form from softmin_path(), rows, grid and block from softmin_launch().
+// (hipcc emits the template kernels in the order they are named here: profiles/sinkhorn_plan.md)
+template <int D>
+void launch_softmin(Path path, bool grad, const SoftminLaunch& l, const DenseArgs& a, const DenseSplit& sp, hipStream_t st) {
+  const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  const bool wide = l.rows == kMRowsWide;
+  if (!grad) {
+    if constexpr (D == 16) {
+      if (path == Path::MatrixPipe) {
+        if (wide) hipLaunchKernelGGL(dense_softmin_mfma_kernel<4>, grid, block, 0, st, a, sp);
+        else hipLaunchKernelGGL(dense_softmin_mfma_kernel<2>, grid, block, 0, st, a, sp);
+      } else if (path == Path::Screened) {
+        if (wide) hipLaunchKernelGGL((dense_softmin_screen_kernel<false, 4>), grid, block, 0, st, a, sp);
+        else hipLaunchKernelGGL((dense_softmin_screen_kernel<false, 2>), grid, block, 0, st, a, sp);
+      }
+    }
+    if (path == Path::Difference) hipLaunchKernelGGL((dense_softmin_kernel<D, false>), grid, block, 0, st, a);
+  } else {
+    if constexpr (D == 16) {
+      if (path == Path::MatrixPipe) {
+        hipLaunchKernelGGL(dense_softmin_mfma_grad_kernel, grid, block, 0, st, a, sp);
+      } else if (path == Path::Screened) {
+        if (wide) hipLaunchKernelGGL((dense_softmin_screen_kernel<true, 4>), grid, block, 0, st, a, sp);
+        else hipLaunchKernelGGL((dense_softmin_screen_kernel<true, 2>), grid, block, 0, st, a, sp);
+      }
+    }
+    if (path == Path::Difference) hipLaunchKernelGGL((dense_softmin_kernel<D, true, 4>), grid, block, 0, st, a);
+  }
+}
+
 template <int D>
 int run_dense(const float* x, const float* alpha, const float* y, const float* beta, int N, int M, float blur,
               float scaling, float reach, double diameter, float* ws, float* loss, float* gx, float* galpha,
               hipStream_t st) {
-  // workspace: la (N) | lb (M) | pot A (2N+2M) | pot B (2N+2M) | grad_xx (N*D) | grad_xy (N*D)
-  float* la = ws;
-  float* lb = la + N;
-  float* potA = lb + M;
-  float* potB = potA + 2 * (size_t)(N + M);
-  float* gxx = potB + 2 * (size_t)(N + M);
-  float* gxy = gxx + (size_t)N * D;
-  float* center = gxy + (size_t)N * D;            // 16 floats (of the 64-float pad)
-  float* n2 = center + 64;                        // (N + M) floats, then the prepared points: (N + M) x 96 B
-  char* splits = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(n2 + (size_t)(N + M)) + 15) & ~(uintptr_t)15);
-  const bool use_mfma = D == 16 && kd6d_opt(KD6D_OPT_SINKHORN_DENSE_MFMA) != 0;
-  DenseSplit sp;
-  sp.xs = splits; sp.ys = splits + (size_t)N * kSplitBytes; sp.xn2 = n2; sp.yn2 = n2 + N;
-  const size_t n128 = ((size_t)N + 127) & ~(size_t)127, m128 = ((size_t)M + 127) & ~(size_t)127;
-  char* yt0 = splits + ((size_t)N + M) * kSplitBytes;          // 16-byte aligned: kSplitBytes is a multiple of 16
-  sp.xt = yt0; sp.yt = yt0 + n128 * kYtBytes;
-  if (use_mfma) {
-    // (the partial sums borrow the head of the A-operand array: dense_split_kernel fills it afterwards; >= 4096 floats)
-    float* partials = reinterpret_cast<float*>(yt0);
+  const DenseOptions opt = {kd6d_opt(KD6D_OPT_SINKHORN_DENSE_MFMA), kd6d_opt(KD6D_OPT_SINKHORN_DENSE_SCREEN),
+                            kd6d_opt(KD6D_OPT_SINKHORN_DENSE_ROWS)};
+  const DenseWorkspace w = dense_workspace(N, M, D, (int)(reinterpret_cast<uintptr_t>(ws) & 15));
+  char* const base = reinterpret_cast<char*>(ws);
+  auto floats = [&](const Region& r) { return reinterpret_cast<float*>(base + r.off); };
+  float* la = floats(w.la);
+  float* lb = floats(w.lb);
+  float* gxx = floats(w.grad_xx);
+  float* gxy = floats(w.grad_xy);
+  const DenseSplit sp = {base + w.xs.off, base + w.ys.off, floats(w.n2), floats(w.n2) + N, base + w.xt.off, base + w.yt.off};
+  if (D == 16 && opt.mfma != 0) {
+    float* center = floats(w.center);
+    float* partials = floats(w.partials);
     hipLaunchKernelGGL(dense_center_kernel, dim3(kCenterWgs), dim3(256), 0, st, x, (long long)N * D, D, partials);
     hipLaunchKernelGGL(dense_center_kernel, dim3(kCenterWgs), dim3(256), 0, st, y, (long long)M * D, D, partials + kCenterWgs * 16);
     hipLaunchKernelGGL(dense_center_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)partials, 2 * kCenterWgs, D, center);
     const float inv_count = 1.0f / (float)((long long)N + M);
-    hipLaunchKernelGGL(dense_split_kernel, dim3((unsigned)(n128 / 256 + 1)), dim3(256), 0, st, x, N, (const float*)center, inv_count,
-                       splits, n2, yt0);
-    hipLaunchKernelGGL(dense_split_kernel, dim3((unsigned)(m128 / 256 + 1)), dim3(256), 0, st, y, M, (const float*)center, inv_count,
-                       splits + (size_t)N * kSplitBytes, n2 + N, yt0 + n128 * kYtBytes);
+    // one thread per point of the padded set, and one more workgroup as before
+    hipLaunchKernelGGL(dense_split_kernel, dim3((unsigned)(w.xt.bytes / kYtBytes / 256 + 1)), dim3(256), 0, st, x, N,
+                       (const float*)center, inv_count, base + w.xs.off, floats(w.n2), base + w.xt.off);
+    hipLaunchKernelGGL(dense_split_kernel, dim3((unsigned)(w.yt.bytes / kYtBytes / 256 + 1)), dim3(256), 0, st, y, M,
+                       (const float*)center, inv_count, base + w.ys.off, floats(w.n2) + N, base + w.yt.off);
   }
   hipLaunchKernelGGL(dense_logw_kernel, dim3((N + 255) / 256), dim3(256), 0, st, alpha, la, N);
   hipLaunchKernelGGL(dense_logw_kernel, dim3((M + 255) / 256), dim3(256), 0, st, beta, lb, M);
-  // epsilon schedule in double, like the reference's python floats (geomloss epsilon_schedule, p = 2)
-  if (diameter < 1e-12) diameter = 1e-12;
-  const double e_start = 2.0 * log(diameter), e_stop = 2.0 * log((double)blur), e_step = 2.0 * log((double)scaling);
-  int n_ar = 0;
-  if (e_step < 0.0 && e_start > e_stop) n_ar = (int)ceil((e_stop - e_start) / e_step);
-  if (n_ar < 0) n_ar = 0;
-  if (n_ar > 4096) n_ar = 4096;
-  const int n_eps = n_ar + 2;
-  const double rho = reach > 0.f ? (double)reach * (double)reach : -1.0;
-  auto eps_at = [&](int i) -> double {
-    if (i == 0) return diameter * diameter;
-    if (i <= n_ar) return exp(e_start + (double)(i - 1) * e_step);
-    return (double)blur * (double)blur;
-  };
+  const EpsSchedule sched(diameter, blur, scaling, reach);
   const int nmax = N > M ? N : M;
-  const dim3 grid((nmax + kRows - 1) / kRows, 4);
+  const int mrows = matrix_rows(nmax, opt.rows);
   DenseArgs a;
   a.x = x; a.y = y; a.la = la; a.lb = lb; a.N = N; a.M = M; a.grad_xx = gxx; a.grad_xy = gxy;
-  float* cur = potA;
-  float* nxt = potB;
-  // the matrix-pipe kernel while the cancellation of its |r|^2 + |c|^2 - 2 r.c form stays below ~1e-4 in the exponent
-  // (header of dense_softmin_mfma_kernel): eps >= kMfmaEpsRel * diameter^2; option sinkhorn.dense_mfma: 0 = never,
-  // 1 = by that rule, 2 = every gradient-free pass (tests: how wrong it gets)
-  const double mfma_eps_min = kd6d_opt(KD6D_OPT_SINKHORN_DENSE_MFMA) == 2 ? 0.0 : kMfmaEpsRel * diameter * diameter;
-  // rows per workgroup of the matrix-pipe softmins: every workgroup streams ALL columns (108-172 bytes each) through LDS,
-  // so the launch moves (rows / rows-per-workgroup) x columns x bytes from L2 -- 1.8-2.9 GB at N = M = 16384 with 64
-  // rows, which is what bounds it (6-9 TB/s); 128 rows (8 waves) halve that.  Option sinkhorn.dense_rows: -1 = 128 from
-  // 8192 rows up | 64 | 128
-  const long long rows_opt = kd6d_opt(KD6D_OPT_SINKHORN_DENSE_ROWS);
-  const bool rg4 = rows_opt == 128 || (rows_opt != 64 && nmax >= 8192);
-  const int mrows = rg4 ? 128 : kMRows;
-  const dim3 grid_m((nmax + mrows - 1) / mrows, 4);
-  const dim3 block_m(rg4 ? 512 : 256);
-  auto launch = [&](int mode, double eps, bool grad) {
+  float* cur = floats(w.pot[0]);
+  float* nxt = floats(w.pot[1]);
+  auto set_which = [&](int w0, int w1, int w2, int w3) { a.which[0] = w0; a.which[1] = w1; a.which[2] = w2; a.which[3] = w3; };
+  // one epsilon step: all four softmins; last: the extrapolation that carries the gradient
+  auto pass = [&](int mode, double eps, bool last) {
     a.pot_old = cur; a.pot_new = nxt; a.mode = mode; a.eps = (float)eps;
-    a.lam = rho > 0.0 ? (float)(1.0 / (1.0 + eps / rho)) : 1.f;
-    const bool mfma_ok = use_mfma && eps >= mfma_eps_min;
-    // below the rule: the matrix pipe screens, the difference form evaluates what passes (dense_softmin_screen_kernel).
-    // Threshold: 40 + twice the bound of the approximate exponent's error, k2 2^-21 S with S <= diameter^2 (centred points)
-    const bool screen_ok = use_mfma && !mfma_ok && kd6d_opt(KD6D_OPT_SINKHORN_DENSE_SCREEN) != 0;
-    a.screen_th = (float)(40.0 + (0.5 / eps) * 1.4426950408889634 * diameter * diameter * (1.0 / 1048576.0));
-    auto set_which = [&](int w0, int w1, int w2, int w3) { a.which[0] = w0; a.which[1] = w1; a.which[2] = w2; a.which[3] = w3; };
-    if (!grad) {
+    a.lam = sched.lam(eps);
+    a.screen_th = screen_threshold(eps, sched.diameter);
+    const Path plain = softmin_path(D, eps, sched.diameter, opt, false);
+    if (!last) {
       set_which(0, 1, 2, 3);
-      if (mfma_ok) {
-        if constexpr (D == 16) {
-          if (rg4) hipLaunchKernelGGL(dense_softmin_mfma_kernel<4>, grid_m, block_m, 0, st, a, sp);
-          else hipLaunchKernelGGL(dense_softmin_mfma_kernel<2>, grid_m, block_m, 0, st, a, sp);
-        }
-      } else if (screen_ok) {
-        if constexpr (D == 16) {
-          if (rg4) hipLaunchKernelGGL((dense_softmin_screen_kernel<false, 4>), grid_m, block_m, 0, st, a, sp);
-          else hipLaunchKernelGGL((dense_softmin_screen_kernel<false, 2>), grid_m, block_m, 0, st, a, sp);
-        }
-      } else {
-        hipLaunchKernelGGL((dense_softmin_kernel<D, false>), grid, dim3(kThreadsD), 0, st, a);
-      }
+      launch_softmin<D>(plain, false, softmin_launch(plain, false, 4, N, M, mrows), a, sp, st);
     } else {
-      // the last extrapolation: only the two softmins over the rows of x (a_x, b_x) carry a gradient -- difference form,
-      // with the softmax-weighted sums; the other two (b_y, a_y) are plain potentials
+      // only the two softmins over the rows of x (a_x, b_x) carry a gradient, with the softmax-weighted sums; the other
+      // two (b_y, a_y) are plain potentials
+      const Path carry = softmin_path(D, eps, sched.diameter, opt, true);
       set_which(0, 3, 0, 0);
-      if (mfma_ok && kd6d_opt(KD6D_OPT_SINKHORN_DENSE_MFMA) != 3) {
-        if constexpr (D == 16)
-          hipLaunchKernelGGL(dense_softmin_mfma_grad_kernel, dim3((N + kMRows - 1) / kMRows, 2), dim3(256), 0, st, a, sp);
-      } else if (screen_ok) {
-        if constexpr (D == 16) {
-          if (rg4) hipLaunchKernelGGL((dense_softmin_screen_kernel<true, 4>), dim3((N + mrows - 1) / mrows, 2), block_m, 0, st, a, sp);
-          else hipLaunchKernelGGL((dense_softmin_screen_kernel<true, 2>), dim3((N + mrows - 1) / mrows, 2), block_m, 0, st, a, sp);
-        }
-      } else {
-        hipLaunchKernelGGL((dense_softmin_kernel<D, true, 4>), dim3((nmax + 127) / 128, 2), dim3(kThreadsD), 0, st, a);
-      }
+      launch_softmin<D>(carry, true, softmin_launch(carry, true, 2, N, M, mrows), a, sp, st);
       set_which(1, 2, 0, 0);
-      if (mfma_ok) {
-        if constexpr (D == 16) {
-          if (rg4) hipLaunchKernelGGL(dense_softmin_mfma_kernel<4>, dim3(grid_m.x, 2), block_m, 0, st, a, sp);
-          else hipLaunchKernelGGL(dense_softmin_mfma_kernel<2>, dim3(grid_m.x, 2), block_m, 0, st, a, sp);
-        }
-      } else if (screen_ok) {
-        if constexpr (D == 16) {
-          if (rg4) hipLaunchKernelGGL((dense_softmin_screen_kernel<false, 4>), dim3(grid_m.x, 2), block_m, 0, st, a, sp);
-          else hipLaunchKernelGGL((dense_softmin_screen_kernel<false, 2>), dim3(grid_m.x, 2), block_m, 0, st, a, sp);
-        }
-      } else {
-        hipLaunchKernelGGL((dense_softmin_kernel<D, false>), dim3(grid.x, 2), dim3(kThreadsD), 0, st, a);
-      }
+      launch_softmin<D>(plain, false, softmin_launch(plain, false, 2, N, M, mrows), a, sp, st);
     }
     float* t = cur; cur = nxt; nxt = t;
   };
-  launch(0, eps_at(0), false);
-  double eps = eps_at(0);
-  for (int it = 0; it < n_eps; ++it) {
-    eps = eps_at(it);
-    launch(1, eps, false);
+  pass(0, sched.at(0), false);
+  double eps = sched.at(0);
+  for (int it = 0; it < sched.n_eps(); ++it) {
+    eps = sched.at(it);
+    pass(1, eps, false);
   }
-  launch(2, eps, true);
-  const float lam = rho > 0.0 ? (float)(1.0 / (1.0 + eps / rho)) : 1.f;
+  pass(2, eps, true);
   int nb = (nmax + 255) / 256;
   if (nb > 512) nb = 512;
   // the other potential buffer (2 (N + M) floats >= nb) is free after the last pass: it takes the per-workgroup partials
-  hipLaunchKernelGGL(dense_finalize_kernel<D>, dim3(nb), dim3(256), 0, st, alpha, beta, cur, N, M, (float)eps, lam,
-                     (float)rho, gxx, gxy, nxt, gx, galpha);
+  hipLaunchKernelGGL(dense_finalize_kernel<D>, dim3(nb), dim3(256), 0, st, alpha, beta, cur, N, M, (float)eps, sched.lam(eps),
+                     (float)sched.rho, gxx, gxy, nxt, gx, galpha);
   hipLaunchKernelGGL(dense_loss_sum_kernel, dim3(1), dim3(64), 0, st, (const float*)nxt, nb, loss);
   return KD6D_OK;
 }
@@ -1187,11 +1147,7 @@ int run_dense(const float* x, const float* alpha, const float* y, const float* b
 }  // namespace
 
 extern "C" int64_t kd6d_sinkhorn_dense_workspace_floats(int N, int M, int D) {
-  // log weights, two potential sets, two gradient partials, centre (+ pad), and for D = 16 the matrix-pipe softmin's
-  // prepared points: |p|^2 and 96 bytes of bf16 pieces per point
-  // ... and 64 bytes of fp16 pieces per point (sets padded to multiples of 128 points) for the gradient's second product
-  return (int64_t)N + M + 4 * ((int64_t)N + M) + 2 * (int64_t)N * D + 64 +
-         (D == 16 ? 25 * ((int64_t)N + M) + 16 + 16 * ((((int64_t)N + 127) & ~127ll) + (((int64_t)M + 127) & ~127ll)) : 0);
+  return kd6d_sinkhorn::dense_workspace(N, M, D, 0).total_floats;
 }
 
 extern "C" int kd6d_sinkhorn_dense_diameter(const float* x, const float* y, int N, int M, int D, float* scratch64,
