@@ -1047,7 +1047,7 @@ def wgrad_group_supported(geom, dtype):
 
 class WgradGroup:
     """The weight gradients of several layers as one launch pair.  add() collects (geometry, x, dy, dw, dbias);
-    launch() plans the work list on first use (or when the set of tensors changed), keeps the plan and the
+    launch() plans the work list on first use (or when the tensors or their geometry changed), keeps the plan and the
     partial-tile slab on the device, and enqueues the two kernels on the current stream.  The collected tensors
     must stay alive and unchanged until the launch has run (the engine's per-layer buffers are static)."""
 
@@ -1103,8 +1103,10 @@ class WgradGroup:
         """Enqueue on the current stream; clears the collected items."""
         if not self.items:
             return
+        # the plan holds the pointers AND the geometry (levels, channels, kernel size): both are the key, so the same
+        # buffers under other levels of the same row total get a plan of their own
         key = (self.n_workgroups,) + tuple(
-            (x.data_ptr(), dy.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), g.rows_out)
+            (x.data_ptr(), dy.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), bytes(g.c))
             for g, x, dy, dw, db in self.items)
         ent = self._plans.get(key)
         if ent is None:
