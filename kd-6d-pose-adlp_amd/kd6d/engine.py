@@ -16,6 +16,7 @@ import torch
 
 from . import ops
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
+from .wgrad_sched import WgradSchedule
 
 ANCHOR_SIZES = [32, 64, 128, 256, 512]
 ANCHOR_STRIDES = [8, 16, 32, 64, 128]
@@ -293,10 +294,10 @@ class Conv:
 
     def stem_slab(self, g, dtype):
         """The slab of the fused pooled-BatchNorm backward + weight gradient (ops.bn_pool_bwd_wgrad), or None when that
-        launch does not take this geometry (or option stem.fused = 0).  Sized for PoseNet.wgrad_budget(), the budget of
+        launch does not take this geometry (or option stem.fused = 0).  Sized for WgradSchedule.budget(), the budget of
         the separate launch it stands in for: the fused launch splits the pixels as that one does (csrc/conv_plan.h,
         stem_bwd_rule)."""
-        budget = self.net.wgrad_budget()
+        budget = self.net.wgrad.budget()
         key = (id(g), dtype, "stem", budget, ops.get_option("stem.fused"))
         parts = self._parts.get(key)
         if parts is None:
@@ -304,42 +305,10 @@ class Conv:
         return self.net.store.slab(self.w, parts) if parts else None
 
     def bwd(self, x, dy, batch, levels, need_dx=True, dx=None, accumulate=False, need_dw=True):
-        """wgrad (+ bias grad) into the flat grad buffer, then dgrad."""
-        st = self.net.store
+        """wgrad (+ bias grad) where the network's WgradSchedule puts it, then dgrad."""
         g = self.geom(batch, levels)
-        grp = self.net.wgrad_group if self.net.grouping else None
-        if not need_dw:
-            pass
-        elif grp is not None and x.dtype == torch.bfloat16 and ops.wgrad_group_supported(g, x.dtype):
-            # collected: one launch pair for the whole network section (PoseNet.flush_wgrad_group); x and dy are
-            # per-layer buffers that stay untouched until the sweep has joined its side streams
-            grp.add(g, x, dy, st.storage(self.w, "grads"), None if self.b is None else st.storage(self.b, "grads"),
-                    flops=self.flops(g))
-        elif (limit := self.net.wgrad_list_limit()) > 1:
-            # collected: the sweep forks once for several layers and their weight gradients go out as ONE list launch
-            # (PoseNet.flush_wgrad_list).  x is a tensor of the forward tape and dy this layer's own gradient buffer
-            # (draw / d_inner / a slice of d_head_in): the sweep writes neither again, so the later launch reads what
-            # this one would have read (DESIGN.md section 5)
-            budget = self.net.wgrad_budget()
-            self.net._wgrad_pending.append(dict(
-                geom=g, x=x, dy=dy, dw_slab=self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
-                dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride, cu_budget=budget))
-            if len(self.net._wgrad_pending) >= limit:
-                self.net.flush_wgrad_list()
-        elif (side := self.net.next_side_stream()) is None:
-            budget = self.net.wgrad_budget()         # (0: the device)
-            ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
-                             dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride, cu_budget=budget)
-        else:
-            # the weight gradient feeds nothing in the reverse sweep: fork it onto the side stream so it
-            # overlaps the dgrad / normalisation chain (both under-fill 256 CUs at these layer sizes);
-            # PoseNet.backward joins before the gradient exchange.  x and dy are per-layer buffers.
-            budget = self.net.wgrad_budget()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                ops.conv2d_wgrad(g, x, dy, self.wgrad_slab(g, x.dtype, budget), flops=self.flops(g),
-                                 dbias=None if self.b is None else st.acc(self.b), acc_stride=st.acc_stride,
-                                 cu_budget=budget)
+        if need_dw:
+            self.net.wgrad.submit(self, g, x, dy)
         if not need_dx:
             return None
         return ops.conv2d_dgrad(g, dy, self.weight_t(), dx=dx, accumulate=accumulate, flops=self.flops(g))
@@ -494,7 +463,7 @@ class ConvBlock:
                                              w1, w2, replicas=R)
                 ops.bn_pool_bwd_wgrad(g, x, raw, dz, mean, invstd, gamma, beta, ACT_LEAKY, w1, w2,
                                       st.storage(self.bn.gamma, "grads"), st.storage(self.bn.beta, "grads"), slab,
-                                      replicas=R, flops=self.conv.flops(g), cu_budget=net.wgrad_budget())
+                                      replicas=R, flops=self.conv.flops(g), cu_budget=net.wgrad.budget())
                 return None
         draw = net.buf(self.name + ".draw", raw.shape, net.dtype)
         if pooled is not None:                  # dz is the gradient of the pooled output
@@ -565,6 +534,8 @@ class PoseNet:
         self.training = True
         self.in_hw = None
         self.levels, self.batch = None, None
+        # ---- the knobs of the reverse sweep's weight-gradient schedule (wgrad_sched.py reads them when it needs them;
+        # GraphedKDStep / GroupedTeacherKDStep and bench.py set them) ----
         self.side_stream = None        # set (e.g. by GraphedKDStep) to run weight gradients concurrently
         self.side_streams = None       # optional list: consecutive weight gradients rotate over these streams
         self.wgrad_cu_budget = 0       # CUs each forked weight gradient aims to fill (0 = the device)
@@ -572,17 +543,16 @@ class PoseNet:
         # (csrc/conv_wgrad_group.hip); created on first use, bf16 only.  wgrad_group_wgs: workgroups of that launch
         # (0 = one per two CUs).  Measured on the step (images/s, 64 / 128 / 256 workgroups): pipelined 4831 / 4828 /
         # 4788, strictly sequential 4050 / 4164 / 4241 -- GraphedKDStep asks for one per CU in sequential mode
+        self.use_wgrad_group = True
+        self.wgrad_group_wgs = 0
+        self.wgrad_group_flush = "head_end"     # or "fpn_end" (GraphedKDStep picks by launch mode)
+        self.wgrad = WgradSchedule(self, ops)   # ... and its transient state
         # set by GraphedKDStep around its own calls only: the packed NHWC input to use instead of converting `images`
         # (nhwc_in), or where to put the conversion (nhwc_out)
         self.nhwc_in = self.nhwc_out = None
-        self.wgrad_group = None
-        self.grouping = False          # True while the reverse sweep is inside the section whose dW are collected
-        self.use_wgrad_group = True
-        self.wgrad_group_wgs = 0
         # GroupedTeacherKDStep: called at layer-group boundaries of an eval-mode forward (the places where the frozen
         # teacher's pass over several steps' batches may be cut into per-step graph segments)
         self.cut_hook = None
-        self.wgrad_group_flush = "head_end"     # or "fpn_end" (GraphedKDStep picks by launch mode)
         self.grad_hook = None           # called by backward() when the FPN + head gradients have been issued
         self.resolve_hi = None          # backward() resolves the accumulated gradients of [0, resolve_hi) at its end (None: all)
         self.fuse_pool = True           # BN + act + maxpool as one kernel (training)
@@ -604,12 +574,6 @@ class PoseNet:
         self.bn_on_load = 0            # 0 off | 1 where the next block is a 1x1 convolution | 2 every in-stage transition
         # cls / pose tower layers as one launch (training): 0 = off, 1 = forward and data gradients, 2 = forward only
         self.pair_towers = 1
-        self._side_rr = 0
-        # per-layer weight gradients waiting for their fork (Conv.bwd, option wgrad.list); wgrad_list_tail: the sweep is
-        # inside its last blocks, where every layer forks at once again (a list launched behind the last chain kernel
-        # would run alone)
-        self._wgrad_pending = []
-        self.wgrad_list_tail = False
         feat, oc = BACKBONE_CFG[arch]
         self.out_channel = oc
         self.n_levels = 5 if arch == "darknet53" else 4
@@ -761,53 +725,6 @@ class PoseNet:
 
     def fuse_norm_on(self):
         return False if self.fuse_norm is None else bool(self.fuse_norm)
-
-    def wgrad_budget(self):
-        """CU budget of a per-layer weight-gradient launch (ops.conv2d_wgrad, ops.bn_pool_bwd_wgrad): the share
-        wgrad_cu_budget when these launches are forked onto side streams (next_side_stream() gives one), the whole
-        device (0) when they run on the main stream.  The one place that decides it: slab sizes and launches agree."""
-        return self.wgrad_cu_budget if (self.side_streams or self.side_stream is not None) else 0
-
-    def next_side_stream(self):
-        if self.side_streams:
-            self._side_rr = (self._side_rr + 1) % len(self.side_streams)
-            return self.side_streams[self._side_rr]
-        return self.side_stream
-
-    WGRAD_LIST_TAIL_BLOCKS = 2      # blocks at the end of the backbone sweep whose weight gradients fork per layer
-
-    def wgrad_list_limit(self):
-        """How many per-layer weight gradients Conv.bwd collects before one fork (option wgrad.list); 0: a fork per layer
-        -- no side stream to fork onto, the option off, or the end of the sweep."""
-        if self.wgrad_list_tail or not (self.side_streams or self.side_stream is not None):
-            return 0
-        n = ops.get_option("wgrad.list")
-        return n if n > 1 else 0
-
-    def flush_wgrad_list(self):
-        """One fork for the collected per-layer weight gradients: one wait_stream, one side stream, one
-        ops.conv2d_wgrad_list (the transposing-family calls side by side inside list launches)."""
-        calls = self._wgrad_pending
-        if not calls:
-            return
-        self._wgrad_pending = []
-        side = self.next_side_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            ops.conv2d_wgrad_list(calls)
-
-    def flush_wgrad_group(self):
-        """Launch the collected weight gradients (on a side stream when there is one: nothing in the sweep reads dW)."""
-        grp = self.wgrad_group
-        if grp is None or len(grp) == 0:
-            return
-        side = self.next_side_stream()
-        if side is None:
-            grp.launch()
-            return
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            grp.launch()
 
     def workspace(self):
         ws = self._bufs.get("__workspace__")
@@ -1069,10 +986,7 @@ class PoseNet:
         (the Scale module's factor is already folded into dreg by kd6d_loss_backward)."""
         assert self.training
         B, lv_all, r, oc = self.batch, self.levels, self.rows, self.out_channel
-        if self.use_wgrad_group and self.dtype == torch.bfloat16 and self.wgrad_group is None:
-            self.wgrad_group = ops.WgradGroup(self.wgrad_group_wgs or max(ops.device_cu_count() // 2, 1))
-        self.grouping = self.wgrad_group is not None
-        self._wgrad_pending, self.wgrad_list_tail = [], False
+        self.wgrad.begin()
         d_head_in = self.buf("d_head_in", (r, oc))
         first = True
         towers = (("cls", self.cls_tower, self.cls_logits, dcls), ("pose", self.pose_tower, self.pose_pred, dreg))
@@ -1126,24 +1040,14 @@ class PoseNet:
         n_l = len(idxs)
         # d_head_in is complete: the FPN output convolutions' weight gradients (x = the top-down sums kept by the
         # forward, dy = the level slices of d_head_in) join the head's group, which then goes out as one launch pair
+        # here or behind the FPN sweep (WgradSchedule.flush_group)
         grouped_out = set()
-        if self.wgrad_group is not None:
-            for pos in range(n_l):
-                i = idxs[pos]
-                f, lv, inner = self.fpn_ctx[i]
-                conv = self.outc[i]
-                g = conv.geom(B, lv)
-                if ops.wgrad_group_supported(g, inner.dtype):
-                    self.wgrad_group.add(g, inner, dslot(pos), self.store.storage(conv.w, "grads"),
-                                         self.store.storage(conv.b, "grads"), flops=conv.flops(g))
-                    grouped_out.add(i)
-            # launched here, beside the FPN / backbone sweep, when a teacher forward shares the device (pipelined
-            # steps: 5363-5382 images/s against 5107-5135 with the launch behind the FPN sweep); strictly sequential
-            # steps launch it behind the FPN sweep, beside the backbone sweep's chain of small launches (4836 against
-            # 4655).  At the very end of the sweep it costs 2-7 % of the step (it then runs with nothing beside it).
-            if self.wgrad_group_flush != "fpn_end":
-                self.flush_wgrad_group()
-        self.grouping = False
+        for pos, i in enumerate(idxs):
+            f, lv, inner = self.fpn_ctx[i]
+            if self.wgrad.try_group(self.outc[i], self.outc[i].geom(B, lv), inner, dslot(pos)):
+                grouped_out.add(i)
+        self.wgrad.close_group_section()
+        self.wgrad.flush_group("head_end")
         # P7 = conv(relu(P6)); P6 = conv(top feature)
         ftop, lvtop, p6, p6r, h6 = self.p6_ctx
         d_p6r = self.p7.bwd(p6r, dslot(n_l + 1), B, [h6], dx=self.buf("d_p6r", p6.shape))
@@ -1169,38 +1073,22 @@ class PoseNet:
                 dfeat[i] = self.inner[i].bwd(f, d_inner, B, lv, dx=self.buf("dfeat%d" % i, f.shape))
             d_inner_up = (d_inner, h, w)
         ops.mark("student.bwd.fpn.end")
-        if self.wgrad_group is not None and self.wgrad_group_flush == "fpn_end":
-            self.flush_wgrad_group()
+        self.wgrad.flush_group("fpn_end")
         if self.grad_hook is not None:
             # every gradient outside the backbone has been issued (on this stream or on the weight-gradient streams):
             # a data-parallel caller starts their exchange here, beside the backbone sweep
-            self.flush_wgrad_list()
+            self.wgrad.flush_list()
             self.grad_hook()
         if self.arch == "darknet53":
             self._backbone53_bwd(dfeat)
         else:
             self._backbone_tiny_bwd(dfeat[top], dfeat.get(2))
-        self.wgrad_list_tail = False
-        self.flush_wgrad_list()              # (what a sweep shorter than the tail rule left)
-        ops.mark("student.bwd.main.end")
-        for side in (self.side_streams or ([self.side_stream] if self.side_stream is not None else [])):
-            torch.cuda.current_stream().wait_stream(side)
+        self.wgrad.finish()
         # every accumulated gradient (per-layer weight / bias gradients, GroupNorm gains and shifts, the head's scales)
         # -> fp32, accumulators cleared for the next step: one launch.  A caller that resolved the FPN + head part
         # early (grad_hook, the overlapped exchange) sets resolve_hi to where that part begins.
         self.store.resolve_grads(0, self.resolve_hi)
         return None
-
-    def _wgrad_tail_start(self):
-        """Tape index at which the reverse sweep enters its last WGRAD_LIST_TAIL_BLOCKS blocks (a unit counts as one)."""
-        blocks = [i for i, rec in enumerate(self.tape) if rec[0] not in ("stage", "pool", "pooled")]
-        n = min(self.WGRAD_LIST_TAIL_BLOCKS, len(blocks))
-        return blocks[n - 1] if n else -1
-
-    def _enter_wgrad_tail(self):
-        # the lists collected so far go out now, beside the chain kernels still to come; from here on a fork per layer
-        self.flush_wgrad_list()
-        self.wgrad_list_tail = True
 
     def _backbone53_bwd(self, dfeat):
         """Reverse sweep of Darknet-53's backbone over the training tape.  dfeat: stage index (2, 3, 4) -> the FPN's
@@ -1208,11 +1096,11 @@ class PoseNet:
         down-sampling block (accumulate=True into the FPN's buffer)."""
         tape = self.tape
         grad = dfeat[len(self.stages) - 1]
-        tail_at = self._wgrad_tail_start()
+        tail_at = self.wgrad.tail_start(tape)
         for i_rec in range(len(tape) - 1, -1, -1):
             rec = tape[i_rec]
             if i_rec == tail_at:
-                self._enter_wgrad_tail()
+                self.wgrad.enter_tail()
             if rec[0] == "stage":
                 continue
             if rec[0] == "unit":
@@ -1237,11 +1125,11 @@ class PoseNet:
         i_rec = len(self.tape) - 1
         pools_seen = 0
         n_pools = sum(1 for t in self.tape if t[0] == "pool")
-        tail_at = self._wgrad_tail_start()
+        tail_at = self.wgrad.tail_start(self.tape)
         while i_rec >= 0:
             rec = self.tape[i_rec]
             if i_rec == tail_at:
-                self._enter_wgrad_tail()
+                self.wgrad.enter_tail()
             if rec[0] == "pooled":              # the pool lives inside the block's BN kernels; out3 = after pool 2
                 if rec[1] == 2 and pending[2] is not None:
                     grad = ops.eltwise(ops.ELT_ADD, grad, pending[2], self.buf("d_out3", grad.shape))

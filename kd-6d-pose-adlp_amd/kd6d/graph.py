@@ -57,7 +57,7 @@ class GraphedKDStep:
         # grouped head weight gradients: one workgroup per two CUs beside a teacher forward (5284-5292 images/s against
         # 5215-5234 at one per CU and 5208-5214 at two), two per CU when the step is strictly sequential (4553 against 4467)
         snet.wgrad_group_wgs = ops.device_cu_count() // 2 if pipeline else 2 * ops.device_cu_count()
-        snet.wgrad_group_flush = "head_end" if pipeline else "fpn_end"      # measured, see PoseNet.backward
+        snet.wgrad_group_flush = "head_end" if pipeline else "fpn_end"      # measured, see WgradSchedule.flush_group
         self.w_cls, self.w_reg, self.w_kd = (float(w) for w in loss_weights)
         self._w = None                                     # the same weights as a device tensor
         self.cfg_kd = cfg_kd
@@ -93,7 +93,7 @@ class GraphedKDStep:
         communication stream, behind everything the weight-gradient streams and the sweep's stream hold so far."""
         snet = self.student.net
         comm = self.comm_stream
-        for side in [torch.cuda.current_stream()] + list(snet.side_streams or ([snet.side_stream] if snet.side_stream else [])):
+        for side in [torch.cuda.current_stream()] + snet.wgrad.streams():
             comm.wait_stream(side)
         with torch.cuda.stream(comm):
             snet.store.resolve_grads(self._split, snet.store.n_train)      # accumulated FPN + head gradients -> fp32

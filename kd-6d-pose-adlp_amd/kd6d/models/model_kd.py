@@ -357,7 +357,7 @@ class PoseModuleKD(nn.Module):
             comm = self._comm_stream = getattr(self, "_comm_stream", None) or torch.cuda.Stream()
 
             def early():
-                for side in [torch.cuda.current_stream()] + list(net.side_streams or ([net.side_stream] if net.side_stream else [])):
+                for side in [torch.cuda.current_stream()] + net.wgrad.streams():
                     comm.wait_stream(side)
                 with torch.cuda.stream(comm):
                     st.resolve_grads(split, st.n_train)      # the accumulated FPN + head gradients -> fp32 first

@@ -62,12 +62,12 @@ def test_replayed_steps_do_not_depend_on_wgrad_list(gpu_device):
             student._debug_keys = keys
             opt = FusedClipAdamW(student, lr=1e-3)
             gs = GraphedKDStep(teacher, student, opt, (0.1, 1.0, 5.0), pipeline=False)
-            flush = student.net.flush_wgrad_list
+            flush = student.net.wgrad.flush_list
 
             def counted():
-                forks.append(len(student.net._wgrad_pending))
+                forks.append(len(student.net.wgrad.pending))
                 flush()
-            student.net.flush_wgrad_list = counted
+            student.net.wgrad.flush_list = counted
             hist = []
             for it in range(3):
                 ld = gs(*batches[it % 2])

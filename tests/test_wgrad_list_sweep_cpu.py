@@ -1,7 +1,7 @@
 """CPU: where the reverse sweep launches its per-layer weight gradients under option wgrad.list, with the device work
 replaced by a ledger (kd6d.engine's `ops` records every launch with the tensors it reads and writes; streams are
 recording stand-ins).  A real PoseNet of either backbone runs a real forward + backward walk on small CPU tensors, so the
-code under test is Conv.bwd, PoseNet.flush_wgrad_list, the flush points of PoseNet.backward and of both backbone sweeps
+code under test is Conv.bwd, WgradSchedule, the flush points of PoseNet.backward and of both backbone sweeps
 (unit_bwd included).  For wgrad.list = 0, 2, 3 and 4:
   * every layer's weight gradient is issued exactly once;
   * after the launch that produces its dy, before the final join, and -- the FPN / head part -- before grad_hook;
@@ -158,12 +158,12 @@ def _sweep(led, arch, value, hook=True):
         conv_.weight = lambda: None
         conv_.weight_t = lambda: None
         conv_.bias = lambda: None
-    enter_tail = net._enter_wgrad_tail
+    enter_tail = net.wgrad.enter_tail
 
     def tail():
         led.events.append(("tail",))
         enter_tail()
-    net._enter_wgrad_tail = tail
+    net.wgrad.enter_tail = tail
     B, H = 1, 64
     with real_ops.option("wgrad.list", value):
         net.forward(torch.zeros(B, 3, H, H))
@@ -230,7 +230,7 @@ def test_sweep_issues_every_weight_gradient_once_and_in_time(ledger, arch):
         n_fpn = sum(1 for b in born if b < hook)
         n_pre = sum(1 for b in born if hook < b < tail)
         n_tail = sum(1 for b in born if b > tail)
-        assert n_fpn >= 2 and n_pre >= 5 and n_tail >= net.WGRAD_LIST_TAIL_BLOCKS, (n_fpn, n_pre, n_tail)
+        assert n_fpn >= 2 and n_pre >= 5 and n_tail >= net.wgrad.WGRAD_LIST_TAIL_BLOCKS, (n_fpn, n_pre, n_tail)
         sections.setdefault(arch, (n_fpn, n_pre, n_tail))
         assert sections[arch] == (n_fpn, n_pre, n_tail), "the option changed which section a layer belongs to"
         v = max(value, 1)
@@ -250,12 +250,12 @@ def test_no_side_stream_no_list(ledger):
     """Eager path without a side stream: the option changes nothing, every weight gradient runs on the chain's stream."""
     led = ledger
     net = engine.PoseNet("darknet_tiny_h", dtype=torch.bfloat16)
-    assert net.wgrad_list_limit() == 0
+    assert net.wgrad.list_limit() == 0
     net.side_stream = Stream(led, "side0")
     with real_ops.option("wgrad.list", 4):
-        assert net.wgrad_list_limit() == 4
-        net.wgrad_list_tail = True
-        assert net.wgrad_list_limit() == 0
+        assert net.wgrad.list_limit() == 4
+        net.wgrad.tail = True
+        assert net.wgrad.list_limit() == 0
     with real_ops.option("wgrad.list", 1):
-        net.wgrad_list_tail = False
-        assert net.wgrad_list_limit() == 0
+        net.wgrad.tail = False
+        assert net.wgrad.list_limit() == 0
