@@ -11,6 +11,7 @@ models/model.py:40-103 (FPN), :370-451 (PoseHead).  Parameter NAMES and logical 
 reference state_dict; storage is KRSC with channels padded to multiples of 8.
 """
 import math
+from collections import namedtuple
 
 import torch
 
@@ -31,8 +32,47 @@ BACKBONE_CFG = {  # arguments/argument.py:59-68
 }
 
 
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1      # every BatchNorm of the reference (torch defaults)
+
+
 def _pad8(c):
     return (c + 7) // 8 * 8
+
+
+# ----------------------------------------------------------------------------------------
+# the training tape (PoseNet.tape): what the forward walk of the backbone leaves for the reverse sweep, in forward
+# order.  `is_block`: the record counts as a block for WgradSchedule.tail_start (a DarkUnit is one block).
+# ----------------------------------------------------------------------------------------
+class BlockRec(namedtuple("BlockRec", "block x raw batch levels pooled")):
+    """One ConvBlock: its input x (what the weight gradient reads), the fp32 convolution output raw, the geometry key
+    (batch, levels), and pooled = (h, w) of the convolution output when BatchNorm ran fused with MaxPool2d(2,2)."""
+    __slots__ = ()
+    is_block = True
+
+
+class UnitRec(namedtuple("UnitRec", "conv1 conv2")):
+    """One DarkUnit: the BlockRecs of its two blocks."""
+    __slots__ = ()
+    is_block = True
+
+
+class PoolRec(namedtuple("PoolRec", "stage x batch h w")):
+    """The separate MaxPool2d(2,2) behind stage `stage` (0-based) of a darknet-tiny backbone and its input."""
+    __slots__ = ()
+    is_block = False
+
+
+class Marker(namedtuple("Marker", "kind stage")):
+    """End of stage `stage`: kind "stage" (Darknet-53) or "pooled" (darknet-tiny, the pool fused into the last block)."""
+    __slots__ = ()
+    is_block = False
+
+
+# the arguments every train-mode BatchNorm launch ends with, and the block's slice of the zeroed arena
+BNArgs = namedtuple("BNArgs", "gamma beta eps momentum running_mean running_var save_mean save_invstd act")
+BlockScratch = namedtuple("BlockScratch", "ssum ssq mean invstd w1 w2 barrier stats")
+# a block whose BatchNorm + LeakyReLU the NEXT block's convolution applies while it loads its input
+Pending = namedtuple("Pending", "block raw sums bn")
 
 
 # ----------------------------------------------------------------------------------------
@@ -330,7 +370,7 @@ class BatchNorm:
         """eval-mode scale/shift (computed once per weight load; torch ops = plumbing)."""
         if self.fold is None:
             st = self.net.store
-            scale = st.storage(self.gamma) * torch.rsqrt(st.storage(self.rv) + 1e-5)
+            scale = st.storage(self.gamma) * torch.rsqrt(st.storage(self.rv) + BN_EPS)
             shift = st.storage(self.beta) - st.storage(self.rm) * scale
             self.fold = (scale.contiguous(), shift.contiguous())
         return self.fold
@@ -346,16 +386,35 @@ class ConvBlock:
         """Replica rows of the backward reduction's accumulators (kd6d.h): from 64 workgroups up."""
         return 8 if rows >= (1 << 14) else 1
 
-    def scratch_floats(self, rows):
-        """fp32 slots of the block's slice of the per-step zeroed arena: {sum, sumsq} accumulators of the batch statistics,
-        saved mean / invstd, the backward's R replica rows of two accumulator sums, its barrier words."""
+    def _scratch_sizes(self, rows):
+        """THE layout of the block's slice of the per-step zeroed arena, in fp32 slots and in order (BlockScratch): the
+        {sum, sumsq} accumulators of the batch statistics, saved mean / invstd, the backward's R replica rows of two
+        accumulator sums, its barrier words.  An accumulator (kd6d_acc, kd6d.h) takes ACC_FLOATS slots."""
         c, A, R = self.conv.cout_p, ops.ACC_FLOATS, self.bwd_replicas(rows)
-        return (2 * A + 2 + 2 * A * R) * c + ops.BARRIER_WORDS
+        return (A * c, A * c, c, c, A * R * c, A * R * c, ops.BARRIER_WORDS)
+
+    def scratch_floats(self, rows):
+        return sum(self._scratch_sizes(rows))
+
+    def scratch_views(self, rows):
+        """The named views of that slice for a convolution output of `rows` rows; `stats` is ssum and ssq as the one
+        {sum, sumsq} tensor the convolution epilogue takes."""
+        hit = self._views.get(rows)
+        if hit is None or hit[0] is not self.net.scratch_buf:       # first use, or the arena moved (PoseNet.to)
+            sizes = self._scratch_sizes(rows)
+            s = self.net.scratch(self.name, sum(sizes))
+            views, o = [], 0
+            for n in sizes:
+                views.append(s[o:o + n])
+                o += n
+            hit = self._views[rows] = (self.net.scratch_buf, BlockScratch(*views, stats=s[0:sizes[0] + sizes[1]]))
+        return hit[1]
 
     def __init__(self, net, name, cin, cout, k, stride=1):
         self.net, self.name = net, name
         self.conv = Conv(net, name + ".conv", cin, cout, k, stride, bias=False)
         self.bn = BatchNorm(net, name + ".bn", self.conv.cout_p)
+        self._views = {}        # rows -> (the arena they were cut from, BlockScratch)
         assert self.conv.cout_p == cout, "BN channels must already be a multiple of 8"
 
     def fwd_eval(self, x, batch, levels, residual=None):
@@ -363,118 +422,115 @@ class ConvBlock:
         y, g = self.conv.fwd(x, batch, levels, scale=sc, shift=sh, act=ACT_LEAKY, residual=residual)
         return y, g.levels_out
 
-    def fwd_train(self, x, batch, levels, tape, pool=False, pending=None, defer=False, residual=None):
-        """residual: a tensor of the output's shape and dtype added after the activation (the DarkUnit's identity,
-        backbone/darknet53.py:54-58; kd6d_bn_train_fwd_res); only on the plain path (no pooling, deferral or fusion).
-        pool=True: the block is followed by MaxPool2d(2,2) (darknet.py:94-97); normalisation, activation and
-        pooling run as one kernel and only the pooled tensor is stored (csrc/norm_ops.hip, bn_pool_*).
-        defer=True: this block's BatchNorm + LeakyReLU is NOT launched here -- the next block of the stage applies it
-        while it loads its input (kd6d_conv2d_fwd_block); returns (None, levels, pending record for that block).
-        pending: the record of the previous block when ITS normalisation was deferred to this convolution (x is None)."""
-        net, st = self.net, self.net.store
-        # the pre-BN tensor stays fp32 (also in bf16 mode): (x - mean) must not cancel bf16 rounding
-        c = self.conv.cout_p
+    def _train_ctx(self, batch, levels):
+        """(geometry, arena views, BatchNorm argument bundle) of a training forward."""
+        st, bn = self.net.store, self.bn
         geom = self.conv.geom(batch, levels)
-        A = ops.ACC_FLOATS         # fp32 slots of one accumulator: the sums are kd6d_acc (reproducible reductions, kd6d.h)
-        s = net.scratch(self.name, self.scratch_floats(geom.rows_out))
-        ssum, ssq = s[0:A * c], s[A * c:2 * A * c]
-        mean, invstd = s[2 * A * c:(2 * A + 1) * c], s[(2 * A + 1) * c:(2 * A + 2) * c]
+        sv = self.scratch_views(geom.rows_out)
+        return geom, sv, BNArgs(st.storage(bn.gamma), st.storage(bn.beta), BN_EPS, BN_MOMENTUM, st.storage(bn.rm),
+                                st.storage(bn.rv), sv.mean, sv.invstd, ACT_LEAKY)
+
+    def fwd_train(self, x, batch, levels, tape, pool=False, residual=None):
+        """-> (z, levels of z); one BlockRec on the tape.
+        residual: a tensor of the output's shape and dtype added after the activation (the DarkUnit's identity,
+        backbone/darknet53.py:54-58; kd6d_bn_train_fwd_res); only on the separate normalise launch (no pooling or fusion).
+        pool=True: the block is followed by MaxPool2d(2,2) (darknet.py:94-97); normalisation, activation and
+        pooling run as one kernel and only the pooled tensor is stored (csrc/norm_ops.hip, bn_pool_*)."""
+        net = self.net
+        geom, sv, bn = self._train_ctx(batch, levels)
+        # the pre-BN tensor stays fp32 (also in bf16 mode): (x - mean) must not cancel bf16 rounding
+        raw = net.buf(self.name + ".raw", (geom.rows_out, self.conv.cout_p), torch.float32)
         if residual is not None:
-            assert not pool and pending is None and not defer and not net.fuse_norm_on(), \
+            assert not pool and not net.fuse_norm_on(), \
                 "ConvBlock.fwd_train: the residual add runs only on the separate normalise launch"
-        if pending is not None or defer:
-            raw = net.buf(self.name + ".raw", (geom.rows_out, c), torch.float32)
-            bn_in = z_in = None
-            if pending is not None:
-                prev, raw_prev, sums_prev, mean_prev, invstd_prev = pending
-                pst = prev.bn
-                bn_in = dict(sums=sums_prev, replicas=ops.BN_REPLICAS, gamma=st.storage(pst.gamma), beta=st.storage(pst.beta),
-                             act=ACT_LEAKY, eps=1e-5, momentum=0.1, running_mean=st.storage(pst.rm),
-                             running_var=st.storage(pst.rv), save_mean=mean_prev, save_invstd=invstd_prev)
-                z_in = net.buf(prev.name + ".z", raw_prev.shape, net.dtype)     # written by this launch: what wgrad reads
-                x = raw_prev
-            if defer:          # the consumer adds the replica rows
-                stats, reps = net.scratch(self.name + ".sums", ops.BN_REPLICAS * 2 * c * A), ops.BN_REPLICAS
-            else:              # bn_train_fwd / bn_pool_train_fwd below read plain {sum, sumsq}
-                stats, reps = s[0:2 * A * c], 1
-            fused = defer or geom.rows_out <= self.FUSE_STATS_MAX_ROWS
-            ops.conv2d_fwd_block(geom, x, self.conv.weight(), raw, stats=stats if fused else None, stats_replicas=reps,
-                                 bn_in=bn_in, z_out=z_in, flops=self.conv.flops(geom))
-            g = geom
-            x_saved = z_in if pending is not None else x
-            if defer:
-                tape.append((self, x_saved, raw, batch, tuple(levels), None))
-                return None, g.levels_out, (self, raw, stats, mean, invstd)
-            if not fused:
-                ops.colstats(raw, ssum, ssq)
-            x = x_saved
-        else:
-            if not pool and net.fuse_norm_on() and self.conv.norm_fusable(batch, levels, ops.NORM_BATCH):
-                # conv -> batch statistics -> normalise + LeakyReLU as ONE launch (grid barrier in the epilogue)
-                raw = net.buf(self.name + ".raw", (geom.rows_out, c), torch.float32)
-                z = net.buf(self.name + ".z", raw.shape, net.dtype)
-                _, g = self.conv.fwd_norm(x, batch, levels, z, ops.NORM_BATCH, st.storage(self.bn.gamma), st.storage(self.bn.beta),
-                                          ACT_LEAKY, raw_out=raw, eps=1e-5, momentum=0.1, running_mean=st.storage(self.bn.rm),
-                                          running_var=st.storage(self.bn.rv), save_mean=mean, save_invstd=invstd)
-                tape.append((self, x, raw, batch, tuple(levels), None))
-                return z, g.levels_out, None
-            # batch statistics come out of the conv epilogue; for the long, narrow first layers (hundreds of
-            # workgroups would add into the same 8..64 addresses) a separate reduction pass is cheaper
-            fused = geom.rows_out <= self.FUSE_STATS_MAX_ROWS
-            raw, g = self.conv.fwd(x, batch, levels, out_f32=True,
-                                   out=net.buf(self.name + ".raw", (geom.rows_out, c), torch.float32),
-                                   stats=s[0:2 * A * c] if fused else None, stats_groups=0)
-            if not fused:
-                ops.colstats(raw, ssum, ssq)
+        if not pool and net.fuse_norm_on() and self.conv.norm_fusable(batch, levels, ops.NORM_BATCH):
+            # conv -> batch statistics -> normalise + LeakyReLU as ONE launch (grid barrier in the epilogue)
+            z = net.buf(self.name + ".z", raw.shape, net.dtype)
+            self.conv.fwd_norm(x, batch, levels, z, ops.NORM_BATCH, bn.gamma, bn.beta, bn.act, raw_out=raw, eps=bn.eps,
+                               momentum=bn.momentum, running_mean=bn.running_mean, running_var=bn.running_var,
+                               save_mean=bn.save_mean, save_invstd=bn.save_invstd)
+            tape.append(BlockRec(self, x, raw, batch, tuple(levels), None))
+            return z, geom.levels_out
+        # batch statistics come out of the conv epilogue; for the long, narrow first layers (hundreds of
+        # workgroups would add into the same 8..64 addresses) a separate reduction pass is cheaper
+        fused = geom.rows_out <= self.FUSE_STATS_MAX_ROWS
+        self.conv.fwd(x, batch, levels, out_f32=True, out=raw, stats=sv.stats if fused else None, stats_groups=0)
+        if not fused:
+            ops.colstats(raw, sv.ssum, sv.ssq)
+        return self._normalise(x, raw, geom, sv, bn, tape, pool, residual)
+
+    def fwd_train_on_load(self, x, batch, levels, tape, pending, defer, pool=False):
+        """The transform-on-load path (kd6d_conv2d_fwd_block) -> (z, levels of z, Pending or None).
+        pending: the previous block's record when ITS normalisation was deferred to this convolution (x is None then).
+        defer=True: this block's BatchNorm + LeakyReLU is NOT launched here -- the next block of the stage applies it
+        while it loads its input; z is None and the Pending record for that block is returned."""
+        net = self.net
+        geom, sv, bn = self._train_ctx(batch, levels)
+        c = self.conv.cout_p
+        raw = net.buf(self.name + ".raw", (geom.rows_out, c), torch.float32)
+        bn_in = z_in = None
+        if pending is not None:
+            bn_in = dict(pending.bn._asdict(), sums=pending.sums, replicas=ops.BN_REPLICAS)
+            z_in = net.buf(pending.block.name + ".z", pending.raw.shape, net.dtype)     # written by this launch
+            x = pending.raw
+        if defer:          # the consumer adds the replica rows
+            stats, reps = net.scratch(self.name + ".sums", ops.BN_REPLICAS * 2 * c * ops.ACC_FLOATS), ops.BN_REPLICAS
+        else:              # bn_train_fwd / bn_pool_train_fwd read plain {sum, sumsq}
+            stats, reps = sv.stats, 1
+        fused = defer or geom.rows_out <= self.FUSE_STATS_MAX_ROWS
+        ops.conv2d_fwd_block(geom, x, self.conv.weight(), raw, stats=stats if fused else None, stats_replicas=reps,
+                             bn_in=bn_in, z_out=z_in, flops=self.conv.flops(geom))
+        if pending is not None:
+            x = z_in           # what the weight gradient reads
+        if defer:
+            tape.append(BlockRec(self, x, raw, batch, tuple(levels), None))
+            return None, geom.levels_out, Pending(self, raw, stats, bn)
+        if not fused:
+            ops.colstats(raw, sv.ssum, sv.ssq)
+        return self._normalise(x, raw, geom, sv, bn, tape, pool, None) + (None,)
+
+    def _normalise(self, x, raw, geom, sv, bn, tape, pool, residual):
+        """The normalise launch behind the convolution (pooled, with the residual, or plain) and the tape record."""
+        net, batch, levels = self.net, geom.batch, tuple(geom.levels_in)
         if pool:
-            (h, w), = g.levels_out
-            z = net.buf(self.name + ".zpool", (batch * (h // 2) * (w // 2), c), net.dtype)
-            ops.bn_pool_train_fwd(raw, z, batch, h, w, ssum, ssq, st.storage(self.bn.gamma), st.storage(self.bn.beta),
-                                  1e-5, 0.1, st.storage(self.bn.rm), st.storage(self.bn.rv), mean, invstd, ACT_LEAKY)
-            tape.append((self, x, raw, batch, tuple(levels), (h, w)))
-            return z, [(h // 2, w // 2)], None
+            (h, w), = geom.levels_out
+            z = net.buf(self.name + ".zpool", (batch * (h // 2) * (w // 2), self.conv.cout_p), net.dtype)
+            ops.bn_pool_train_fwd(raw, z, batch, h, w, sv.ssum, sv.ssq, *bn)
+            tape.append(BlockRec(self, x, raw, batch, levels, (h, w)))
+            return z, [(h // 2, w // 2)]
         z = net.buf(self.name + ".z", raw.shape, net.dtype)
         if residual is not None:
-            ops.bn_train_fwd_res(raw, residual, z, ssum, ssq, st.storage(self.bn.gamma), st.storage(self.bn.beta), 1e-5,
-                                 0.1, st.storage(self.bn.rm), st.storage(self.bn.rv), mean, invstd, ACT_LEAKY)
+            ops.bn_train_fwd_res(raw, residual, z, sv.ssum, sv.ssq, *bn)
         else:
-            ops.bn_train_fwd(raw, z, ssum, ssq, st.storage(self.bn.gamma), st.storage(self.bn.beta), 1e-5, 0.1,
-                             st.storage(self.bn.rm), st.storage(self.bn.rv), mean, invstd, ACT_LEAKY)
-        tape.append((self, x, raw, batch, tuple(levels), None))
-        return z, g.levels_out, None
+            ops.bn_train_fwd(raw, z, sv.ssum, sv.ssq, *bn)
+        tape.append(BlockRec(self, x, raw, batch, levels, None))
+        return z, geom.levels_out
 
     def bwd(self, rec, dz, need_dx=True, dx=None, accumulate=False):
-        _, x, raw, batch, levels, pooled = rec
         net, st = self.net, self.net.store
-        c = self.conv.cout_p
-        R, A = self.bwd_replicas(raw.shape[0]), ops.ACC_FLOATS
-        s = net.scratch(self.name, self.scratch_floats(raw.shape[0]))
-        mean, invstd = s[2 * A * c:(2 * A + 1) * c], s[(2 * A + 1) * c:(2 * A + 2) * c]
-        o = (2 * A + 2) * c
-        w1, w2 = s[o:o + A * R * c], s[o + A * R * c:o + 2 * A * R * c]
-        counter = s[o + 2 * A * R * c:o + 2 * A * R * c + ops.BARRIER_WORDS]      # zeroed with the arena at the start of the step
+        x, raw, pooled = rec.x, rec.raw, rec.pooled
+        R = self.bwd_replicas(raw.shape[0])
+        sv = self.scratch_views(raw.shape[0])       # the barrier words were zeroed with the arena at the start of the step
+        gamma, beta = st.storage(self.bn.gamma), st.storage(self.bn.beta)
+        dgamma, dbeta = st.storage(self.bn.gamma, "grads"), st.storage(self.bn.beta, "grads")
         if pooled is not None and not need_dx and x.dtype == torch.bfloat16:
             # nothing but the weight gradient reads the gradient of the convolution output: formed in LDS, never stored
-            g = self.conv.geom(batch, levels)
+            g = self.conv.geom(rec.batch, rec.levels)
             slab = self.conv.stem_slab(g, x.dtype)
             if slab is not None:
-                gamma, beta = st.storage(self.bn.gamma), st.storage(self.bn.beta)
-                ops.bn_pool_train_bwd_reduce(raw, dz, batch, pooled[0], pooled[1], mean, invstd, gamma, beta, ACT_LEAKY,
-                                             w1, w2, replicas=R)
-                ops.bn_pool_bwd_wgrad(g, x, raw, dz, mean, invstd, gamma, beta, ACT_LEAKY, w1, w2,
-                                      st.storage(self.bn.gamma, "grads"), st.storage(self.bn.beta, "grads"), slab,
-                                      replicas=R, flops=self.conv.flops(g), cu_budget=net.wgrad.budget())
+                ops.bn_pool_train_bwd_reduce(raw, dz, rec.batch, pooled[0], pooled[1], sv.mean, sv.invstd, gamma, beta,
+                                             ACT_LEAKY, sv.w1, sv.w2, replicas=R)
+                ops.bn_pool_bwd_wgrad(g, x, raw, dz, sv.mean, sv.invstd, gamma, beta, ACT_LEAKY, sv.w1, sv.w2, dgamma, dbeta,
+                                      slab, replicas=R, flops=self.conv.flops(g), cu_budget=net.wgrad.budget())
                 return None
         draw = net.buf(self.name + ".draw", raw.shape, net.dtype)
         if pooled is not None:                  # dz is the gradient of the pooled output
-            ops.bn_pool_train_bwd(raw, dz, draw, batch, pooled[0], pooled[1], mean, invstd, st.storage(self.bn.gamma),
-                                  st.storage(self.bn.beta), ACT_LEAKY, w1, w2, st.storage(self.bn.gamma, "grads"),
-                                  st.storage(self.bn.beta, "grads"), replicas=R, counter=counter)
+            ops.bn_pool_train_bwd(raw, dz, draw, rec.batch, pooled[0], pooled[1], sv.mean, sv.invstd, gamma, beta,
+                                  ACT_LEAKY, sv.w1, sv.w2, dgamma, dbeta, replicas=R, counter=sv.barrier)
         else:
-            ops.bn_train_bwd(raw, dz, draw, mean, invstd, st.storage(self.bn.gamma), st.storage(self.bn.beta),
-                             ACT_LEAKY, w1, w2, st.storage(self.bn.gamma, "grads"), st.storage(self.bn.beta, "grads"),
-                             replicas=R, counter=counter)
-        return self.conv.bwd(x, draw, batch, levels, need_dx=need_dx, dx=dx, accumulate=accumulate)
+            ops.bn_train_bwd(raw, dz, draw, sv.mean, sv.invstd, gamma, beta, ACT_LEAKY, sv.w1, sv.w2, dgamma, dbeta,
+                             replicas=R, counter=sv.barrier)
+        return self.conv.bwd(x, draw, rec.batch, rec.levels, need_dx=need_dx, dx=dx, accumulate=accumulate)
 
 
 class GroupNormReLU:
@@ -692,7 +748,7 @@ class PoseNet:
         st = self.store
         for _, bn in self.bns:
             if bn.fold is not None:
-                scale = st.storage(bn.gamma) * torch.rsqrt(st.storage(bn.rv) + 1e-5)
+                scale = st.storage(bn.gamma) * torch.rsqrt(st.storage(bn.rv) + BN_EPS)
                 bn.fold[0].copy_(scale)
                 bn.fold[1].copy_(st.storage(bn.beta) - st.storage(bn.rm) * scale)
         self._weights_dirty = True
@@ -778,15 +834,15 @@ class PoseNet:
             assert not self.fuse_norm_on() and not self.bn_on_load, \
                 "darknet53 training runs without fuse_norm and bn_on_load"
             tape = self.tape
-            x, lv = self.init_block.fwd_train(x, B, lv, tape)[:2]
+            x, lv = self.init_block.fwd_train(x, B, lv, tape)
             feats = []
             for i, units in enumerate(self.stages):
                 for u in units:
                     if u[0] == "down":
-                        x, lv = u[1].fwd_train(x, B, lv, tape)[:2]
+                        x, lv = u[1].fwd_train(x, B, lv, tape)
                     else:
                         x, lv = self.unit_fwd_train(u, x, B, lv)
-                tape.append(("stage", i))
+                tape.append(Marker("stage", i))
                 feats.append((x, lv))
             return feats
         x, lv = self.init_block.fwd_eval(x, B, lv)
@@ -805,23 +861,21 @@ class PoseNet:
 
     def unit_fwd_train(self, u, x, B, lv):
         """DarkUnit ("res", conv1 block, conv2 block) in training mode: conv2(conv1(x)) + x with the add behind conv2's
-        LeakyReLU (backbone/darknet53.py:54-58); one ("unit", rec1, rec2) entry on the tape."""
-        tape = self.tape
-        n0 = len(tape)
-        h, _ = u[1].fwd_train(x, B, lv, tape)[:2]
-        y, lv = u[2].fwd_train(h, B, lv, tape, residual=x)[:2]
-        rec1, rec2 = tape[n0:]
-        tape[n0:] = [("unit", rec1, rec2)]
+        LeakyReLU (backbone/darknet53.py:54-58); one UnitRec on the tape."""
+        recs = []
+        h, _ = u[1].fwd_train(x, B, lv, recs)
+        y, lv = u[2].fwd_train(h, B, lv, recs, residual=x)
+        self.tape.append(UnitRec(*recs))
         return y, lv
 
     def unit_bwd(self, rec, grad):
-        """Backward of a ("unit", rec1, rec2) tape entry: grad (the gradient of the unit's output) becomes, in place, the
-        gradient of its input, d_out + conv1's data gradient."""
-        _, rec1, rec2 = rec
-        d_mid = rec2[0].bwd(rec2, grad, dx=self.buf(rec2[0].name + ".dx", rec2[1].shape))
+        """Backward of a UnitRec: grad (the gradient of the unit's output) becomes, in place, the gradient of its input,
+        d_out + conv1's data gradient."""
+        rec1, rec2 = rec.conv1, rec.conv2
+        d_mid = rec2.block.bwd(rec2, grad, dx=self.buf(rec2.block.name + ".dx", rec2.x.shape))
         # written over d_out: on this stream conv2's BatchNorm backward has already consumed d_out, and the forked
         # weight gradients read only x and draw
-        rec1[0].bwd(rec1, d_mid, dx=grad, accumulate=True)
+        rec1.block.bwd(rec1, d_mid, dx=grad, accumulate=True)
         return grad
 
     def _backbone_tiny(self, x, B, lv):
@@ -836,20 +890,24 @@ class PoseNet:
                     # (one launch per block instead of conv [+ statistics] + normalise): stages 3-5; the first two
                     # stages are single blocks
                     nxt_pointwise = (not last) and units[j + 1].conv.k == 1
-                    x, lv, pending = u.fwd_train(x, B, lv, self.tape, pool=(i != n - 1 and last), pending=pending,
-                                                 defer=self.bn_on_load == 2 and not last or (self.bn_on_load == 1 and nxt_pointwise))
+                    defer = self.bn_on_load == 2 and not last or (self.bn_on_load == 1 and nxt_pointwise)
+                    pool = i != n - 1 and last
+                    if pending is None and not defer:
+                        x, lv = u.fwd_train(x, B, lv, self.tape, pool=pool)
+                    else:
+                        x, lv, pending = u.fwd_train_on_load(x, B, lv, self.tape, pending, defer, pool=pool)
                 if i != n - 1:
-                    self.tape.append(("pooled", i))
+                    self.tape.append(Marker("pooled", i))
                 feats.append((x, lv))
                 continue
             for u in units:
-                x, lv = u.fwd_train(x, B, lv, self.tape)[:2] if self.training else u.fwd_eval(x, B, lv)
+                x, lv = u.fwd_train(x, B, lv, self.tape) if self.training else u.fwd_eval(x, B, lv)
             if i != n - 1:
                 (h, w) = lv[0]
                 y = self.buf("pool%d" % i, (B * (h // 2) * (w // 2), x.shape[1]))
                 ops.maxpool2_fwd(x, y, B, h, w)
                 if self.training:
-                    self.tape.append(("pool", x, B, h, w))
+                    self.tape.append(PoolRec(i, x, B, h, w))
                 x, lv = y, [(h // 2, w // 2)]
             feats.append((x, lv))
         # darknet.py:125-135: out4 = stage5(stage4(out3))
@@ -923,61 +981,41 @@ class PoseNet:
         self.head_ctx = {}
         outs = {}
         towers = (("cls", self.cls_tower, self.cls_logits), ("pose", self.pose_tower, self.pose_pred))
-        if self.training and self.pair_towers:
-            # layer by layer through BOTH towers: the two convolutions of a layer have identical geometry and go
-            # out as one launch (ops.conv_pair: 228 tiles of 192x128 instead of 2 x 170 tiles of 128x128)
-            xs = {t: head_in for t, _, _ in towers}
-            saved = {t: [] for t, _, _ in towers}
+        # A group of towers goes through a layer together.  Training with pair_towers: both -- the two convolutions of a
+        # layer have identical geometry and go out as one launch (ops.conv_pair: 228 tiles of 192x128 instead of
+        # 2 x 170 tiles of 128x128).  Otherwise (the frozen teacher among them) tower by tower.
+        groups = [towers] if self.training and self.pair_towers else [towers[:1], towers[1:]]
+        for group in groups:
+            xs = {tname: head_in for tname, _, _ in group}
+            saved = {tname: [] for tname, _, _ in group}
             for li in range(len(self.cls_tower)):
                 raws = {}
                 fuse = self.fuse_norm_on() and all(tower[li][0].norm_fusable(B, levels_all, ops.NORM_GROUP, tower[li][1].groups)
-                                              for _, tower, _ in towers)
-                with ops.conv_pair():
-                    for tname, tower, _ in towers:
+                                                   for _, tower, _ in group)
+                with ops.conv_pair(enabled=len(group) == 2):
+                    for tname, tower, _ in group:
                         conv, gn = tower[li]
-                        raws[tname] = self.buf("%s.raw%d" % (tname, li), (r, oc), torch.float32)
+                        # a fused eval-mode layer (the frozen teacher): the fp32 pre-normalisation tensor is not even stored
+                        raws[tname] = self.buf("%s.raw%d" % (tname, li), (r, oc), torch.float32) \
+                            if self.training or not fuse else None
                         if fuse:
                             gn.fwd_fused(conv, xs[tname], B, levels_all, self.buf("%s.act%d" % (tname, li), (r, oc)),
                                          raw_out=raws[tname])
                         else:
                             conv.fwd(xs[tname], B, levels_all, out_f32=True, out=raws[tname],
                                      stats=gn.stats(B, levels_all), stats_groups=gn.groups)
-                for tname, tower, _ in towers:
-                    gn = tower[li][1]
+                for tname, tower, _ in group:
                     y = self.buf("%s.act%d" % (tname, li), (r, oc))
                     if not fuse:
-                        gn.fwd(raws[tname], B, levels_all, out=y)
+                        tower[li][1].fwd(raws[tname], B, levels_all, out=y)
                     saved[tname].append((xs[tname], raws[tname]))
                     xs[tname] = y
-            for tname, tower, final in towers:
-                seg = self.store.storage(self.scales) if tname == "pose" else None
-                out, _ = final.fwd(xs[tname], B, levels_all, seg_scale=seg, out_f32=True,
-                                   out=self.buf("%s.logits" % tname, (r, final.cout_p), torch.float32))
-                self.head_ctx[tname] = (saved[tname], xs[tname])
-                outs[tname] = out
-            return outs["cls"], outs["pose"]
-        for tname, tower, final in towers:
-            x = head_in
-            saved = []
-            for li, (conv, gn) in enumerate(tower):
-                y = self.buf("%s.act%d" % (tname, li), (r, oc))
-                if self.fuse_norm_on() and conv.norm_fusable(B, levels_all, ops.NORM_GROUP, gn.groups):
-                    # eval mode (the frozen teacher): the fp32 pre-normalisation tensor is not even stored
-                    raw = self.buf("%s.raw%d" % (tname, li), (r, oc), torch.float32) if self.training else None
-                    gn.fwd_fused(conv, x, B, levels_all, y, raw_out=raw)
-                else:
-                    raw, _ = conv.fwd(x, B, levels_all, out_f32=True,
-                                      out=self.buf("%s.raw%d" % (tname, li), (r, oc), torch.float32),
-                                      stats=gn.stats(B, levels_all), stats_groups=gn.groups)
-                    gn.fwd(raw, B, levels_all, out=y)
-                saved.append((x, raw))
-                x = y
                 self._cut()
-            seg = self.store.storage(self.scales) if tname == "pose" else None
-            out, _ = final.fwd(x, B, levels_all, seg_scale=seg, out_f32=True,
-                               out=self.buf("%s.logits" % tname, (r, final.cout_p), torch.float32))
-            self.head_ctx[tname] = (saved, x)
-            outs[tname] = out
+            for tname, _, final in group:
+                seg = self.store.storage(self.scales) if tname == "pose" else None
+                outs[tname], _ = final.fwd(xs[tname], B, levels_all, seg_scale=seg, out_f32=True,
+                                           out=self.buf("%s.logits" % tname, (r, final.cout_p), torch.float32))
+                self.head_ctx[tname] = (saved[tname], xs[tname])
         return outs["cls"], outs["pose"]
 
     # ---- backward (student only) -------------------------------------------------------------
@@ -988,47 +1026,37 @@ class PoseNet:
         B, lv_all, r, oc = self.batch, self.levels, self.rows, self.out_channel
         self.wgrad.begin()
         d_head_in = self.buf("d_head_in", (r, oc))
-        first = True
         towers = (("cls", self.cls_tower, self.cls_logits, dcls), ("pose", self.pose_tower, self.pose_pred, dreg))
-        if self.pair_towers:
+        hw = [h * w for (h, w) in lv_all]
+        first = True            # layer 0: the towers add into d_head_in one after the other, the first not accumulating
+        for group in ([towers] if self.pair_towers else [towers[:1], towers[1:]]):
             dxs = {}
-            for tname, tower, final, dlog in towers:
-                saved, last = self.head_ctx[tname]
-                dxs[tname] = final.bwd(last, dlog, B, lv_all, dx=self.buf("%s.dact" % tname, (r, oc)))
+            for tname, _, final, dlog in group:
+                dxs[tname] = final.bwd(self.head_ctx[tname][1], dlog, B, lv_all, dx=self.buf("%s.dact" % tname, (r, oc)))
             for li in range(len(self.cls_tower) - 1, -1, -1):
-                # the two GroupNorm backwards of the layer as one launch (170 four-wave workgroups each: alone they
-                # are latency-bound and, back to back on one stream, the second waited for the first)
                 draws, items = {}, []
-                for tname, tower, _, _ in towers:
-                    gn = tower[li][1]
+                for tname, tower, _, _ in group:
                     draws[tname] = self.buf("%s.draw%d" % (tname, li), (r, oc))
-                    items.append(gn.bwd_item(self.head_ctx[tname][0][li][1], dxs[tname], B, lv_all, draws[tname]))
-                ops.gn_relu_bwd_pair(items, [h * w for (h, w) in lv_all], B, self.cls_tower[li][1].groups,
-                                     self.store.acc_stride, flags=ops.GN_WS_ZEROED)
-                if li > 0:
-                    # the two data gradients as one launch; the weight gradients fork onto the side streams as usual
-                    with ops.conv_pair(enabled=self.pair_towers == 1):
-                        for tname, tower, _, _ in towers:
-                            conv = tower[li][0]
-                            dxs[tname] = conv.bwd(self.head_ctx[tname][0][li][0], draws[tname], B, lv_all,
-                                                  dx=self.buf("%s.dact" % tname, (r, oc)))
-                else:   # both towers add into d_head_in: one after the other
-                    for k, (tname, tower, _, _) in enumerate(towers):
-                        tower[0][0].bwd(self.head_ctx[tname][0][0][0], draws[tname], B, lv_all, dx=d_head_in,
-                                        accumulate=k > 0)
-            towers = ()
-        for tname, tower, final, dlog in towers:
-            saved, last = self.head_ctx[tname]
-            dx = final.bwd(last, dlog, B, lv_all, dx=self.buf("%s.dact" % tname, (r, oc)))
-            for li in range(len(tower) - 1, -1, -1):
-                conv, gn = tower[li]
-                x_in, raw = saved[li]
-                draw = gn.bwd(raw, dx, B, lv_all, self.buf("%s.draw%d" % (tname, li), (r, oc)))
-                if li > 0:
-                    dx = conv.bwd(x_in, draw, B, lv_all, dx=self.buf("%s.dact" % tname, (r, oc)))
+                    items.append((tower[li][1], self.head_ctx[tname][0][li][1], dxs[tname], B, lv_all, draws[tname]))
+                if len(group) == 2:
+                    # the two GroupNorm backwards of the layer as one launch (170 four-wave workgroups each: alone they
+                    # are latency-bound and, back to back on one stream, the second waited for the first)
+                    ops.gn_relu_bwd_pair([gn.bwd_item(*a) for gn, *a in items], hw, B, items[0][0].groups,
+                                         self.store.acc_stride, flags=ops.GN_WS_ZEROED)
                 else:
-                    conv.bwd(x_in, draw, B, lv_all, dx=d_head_in, accumulate=not first)
-            first = False
+                    (gn, *a), = items
+                    gn.bwd(*a)
+                # the data gradients of a pair as one launch (never layer 0's: they add into the same tensor); the
+                # weight gradients go where the WgradSchedule puts them as usual
+                with ops.conv_pair(enabled=self.pair_towers == 1 and li > 0):
+                    for tname, tower, _, _ in group:
+                        x_in = self.head_ctx[tname][0][li][0]
+                        if li > 0:
+                            dxs[tname] = tower[li][0].bwd(x_in, draws[tname], B, lv_all,
+                                                          dx=self.buf("%s.dact" % tname, (r, oc)))
+                        else:
+                            tower[0][0].bwd(x_in, draws[tname], B, lv_all, dx=d_head_in, accumulate=not first)
+                            first = False
         row0 = self.level_row0
         ops.mark("student.bwd.head.end")
 
@@ -1101,49 +1129,36 @@ class PoseNet:
             rec = tape[i_rec]
             if i_rec == tail_at:
                 self.wgrad.enter_tail()
-            if rec[0] == "stage":
+            if isinstance(rec, Marker):
                 continue
-            if rec[0] == "unit":
+            if isinstance(rec, UnitRec):
                 grad = self.unit_bwd(rec, grad)
                 continue
-            blk = rec[0]
             if i_rec == 0:                      # the init block: no gradient of the image
-                blk.bwd(rec, grad, need_dx=False)
+                rec.block.bwd(rec, grad, need_dx=False)
                 continue
             prev = tape[i_rec - 1]
-            if prev[0] == "stage" and prev[1] in dfeat:
+            if isinstance(prev, Marker) and prev.stage in dfeat:
                 # the first block of the stage after a feature the FPN reads: its data gradient adds into the FPN's
-                grad = blk.bwd(rec, grad, dx=dfeat[prev[1]], accumulate=True)
+                grad = rec.block.bwd(rec, grad, dx=dfeat[prev.stage], accumulate=True)
             else:
-                grad = blk.bwd(rec, grad, dx=self.buf(blk.name + ".dx", rec[1].shape))
+                grad = rec.block.bwd(rec, grad, dx=self.buf(rec.block.name + ".dx", rec.x.shape))
 
     def _backbone_tiny_bwd(self, grad, dfeat2):
         """Reverse sweep of a darknet-tiny backbone over the training tape.  grad: the FPN's gradient of out4 (after
-        stage 5); dfeat2: of out3 (after stage 3), added when the sweep reaches it."""
-        pending = {2: dfeat2}                  # added when the sweep reaches out3 (after pool3)
-        stage_of_pool = {}
-        i_rec = len(self.tape) - 1
-        pools_seen = 0
-        n_pools = sum(1 for t in self.tape if t[0] == "pool")
-        tail_at = self.wgrad.tail_start(self.tape)
-        while i_rec >= 0:
-            rec = self.tape[i_rec]
+        stage 5); dfeat2: of out3 (the pooled output of stage 3), added when the sweep reaches it."""
+        tape = self.tape
+        tail_at = self.wgrad.tail_start(tape)
+        for i_rec in range(len(tape) - 1, -1, -1):
+            rec = tape[i_rec]
             if i_rec == tail_at:
                 self.wgrad.enter_tail()
-            if rec[0] == "pooled":              # the pool lives inside the block's BN kernels; out3 = after pool 2
-                if rec[1] == 2 and pending[2] is not None:
-                    grad = ops.eltwise(ops.ELT_ADD, grad, pending[2], self.buf("d_out3", grad.shape))
-            elif rec[0] == "pool":
-                _, x, b_, h, w = rec
-                pool_idx = n_pools - 1 - pools_seen    # 3,2,1,0
-                pools_seen += 1
-                if pool_idx == 2 and pending[2] is not None:
-                    grad = ops.eltwise(ops.ELT_ADD, grad, pending[2], self.buf("d_out3", grad.shape))
-                dx = self.buf("dpool%d" % pool_idx, x.shape)
-                grad = ops.maxpool2_bwd(x, grad, dx, b_, h, w)
-            else:
-                blk = rec[0]
+            if isinstance(rec, BlockRec):
                 need_dx = i_rec > 0
-                grad = blk.bwd(rec, grad, need_dx=need_dx,
-                               dx=self.buf(blk.name + ".dx", rec[1].shape) if need_dx else None)
-            i_rec -= 1
+                grad = rec.block.bwd(rec, grad, need_dx=need_dx,
+                                     dx=self.buf(rec.block.name + ".dx", rec.x.shape) if need_dx else None)
+                continue
+            if rec.stage == 2 and dfeat2 is not None:   # out3: behind the pool of stage 3, separate or inside its last block
+                grad = ops.eltwise(ops.ELT_ADD, grad, dfeat2, self.buf("d_out3", grad.shape))
+            if isinstance(rec, PoolRec):
+                grad = ops.maxpool2_bwd(rec.x, grad, self.buf("dpool%d" % rec.stage, rec.x.shape), rec.batch, rec.h, rec.w)

@@ -127,8 +127,9 @@ class WgradSchedule:
             self._fork(self.group.launch)
 
     def tail_start(self, tape):
-        """Tape index at which the reverse sweep enters its last WGRAD_LIST_TAIL_BLOCKS blocks (a unit counts as one)."""
-        blocks = [i for i, rec in enumerate(tape) if rec[0] not in ("stage", "pool", "pooled")]
+        """Tape index at which the reverse sweep enters its last WGRAD_LIST_TAIL_BLOCKS blocks (each tape record says
+        whether it is one: a DarkUnit counts as one, markers and pools as none)."""
+        blocks = [i for i, rec in enumerate(tape) if rec.is_block]
         n = min(self.WGRAD_LIST_TAIL_BLOCKS, len(blocks))
         return blocks[n - 1] if n else -1
 

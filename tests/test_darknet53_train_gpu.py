@@ -149,6 +149,7 @@ def test_darkunit_and_stage_vs_oracle_autograd(gpu_device, what):
     """Stage 3 of Darknet-53 (its down-sampling block and 8 DarkUnits; 'unit': its second unit alone) on B = 2, 16x16
     input, fp32, seeded weights: output, input gradient, every parameter gradient and the running statistics against
     oracle.kd_step_ref.ConvBlockRef / DarkUnitRef under torch autograd."""
+    from kd6d.engine import UnitRec
     from oracle import kd_step_ref as O
     dev = gpu_device
     B = 2
@@ -184,17 +185,16 @@ def test_darkunit_and_stage_vs_oracle_autograd(gpu_device, what):
     y = xd
     for u in units:
         if u[0] == "down":
-            y, lv = u[1].fwd_train(y, B, lv, net.tape)[:2]
+            y, lv = u[1].fwd_train(y, B, lv, net.tape)
         else:
             y, lv = net.unit_fwd_train(u, y, B, lv)
     (ho, wo), = lv
     grad = _to_nhwc(dy).to(dev)
-    for i_rec in range(len(net.tape) - 1, -1, -1):
-        rec = net.tape[i_rec]
-        if rec[0] == "unit":
+    for rec in reversed(net.tape):
+        if isinstance(rec, UnitRec):
             grad = net.unit_bwd(rec, grad)
         else:
-            grad = rec[0].bwd(rec, grad, dx=net.buf(rec[0].name + ".dx", rec[1].shape))
+            grad = rec.block.bwd(rec, grad, dx=net.buf(rec.block.name + ".dx", rec.x.shape))
     net.store.resolve_grads()
     torch.cuda.synchronize()
     cout = y_ref.shape[1]

@@ -7,139 +7,11 @@ code under test is Conv.bwd, WgradSchedule, the flush points of PoseNet.backward
   * after the launch that produces its dy, before the final join, and -- the FPN / head part -- before grad_hook;
   * nothing writes a buffer a pending call reads between the point its layer was reached and its launch;
   * the number of forks is what the option implies."""
-import contextlib
-
 import pytest
 import torch
 
 from kd6d import engine, ops as real_ops
-
-# position (or keyword) of the tensor a launch WRITES; everything else it is handed is read
-WRITES = {"image_to_nhwc": "out", "conv2d_fwd": "out", "conv2d_fwd_block": 3, "conv2d_fwd_norm": 3, "conv2d_dgrad": "dx",
-          "eltwise": 3, "upsample2_add": 2, "sumpool2": 1, "maxpool2_fwd": 1, "maxpool2_bwd": 2, "gn_relu_fwd": 1,
-          "bn_train_fwd": 1, "bn_train_fwd_res": 2, "bn_pool_train_fwd": 1, "bn_train_bwd": 2, "bn_pool_train_bwd": 2,
-          "gn_relu_bwd": 2}
-
-
-def _span(t):
-    return (t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size(),
-            t.untyped_storage().data_ptr() + (t.storage_offset() + t.numel()) * t.element_size())
-
-
-def _overlap(a, b):
-    return a[0] < b[1] and b[0] < a[1]
-
-
-class Stream:
-    def __init__(self, ledger, name):
-        self.ledger, self.name = ledger, name
-
-    def wait_stream(self, other):
-        self.ledger.events.append(("wait", self.name, other.name))
-
-
-class Ledger:
-    """Stands in for kd6d.ops inside kd6d.engine."""
-
-    def __init__(self):
-        self.events = []            # (kind, ...) in issue order
-        self.writes = []            # (event index, span)
-        self.current = "main"
-        self.main = Stream(self, "main")
-        self.born = {}              # slab data_ptr -> event index at which its layer's Conv.bwd built the call
-
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-        val = getattr(real_ops, name)
-        if not callable(val) or isinstance(val, type) and name == "Geom" or name in ("get_option", "set_option", "option",
-                                                                                    "wgrad_group_supported", "mark"):
-            return val
-        return lambda *a, **k: self._launch(name, a, k)
-
-    # ---- sizes and switches the engine asks for (no device) ----
-    def device_cu_count(self):
-        return 256
-
-    def conv2d_wgrad_parts(self, *a, **k):
-        return 2
-
-    def bn_pool_bwd_wgrad_parts(self, *a, **k):
-        return 0                    # the fused stem launch is not under test: the stem goes through Conv.bwd
-
-    def conv_norm_fusable(self, *a, **k):
-        return False
-
-    def gn_bwd_workspace_floats(self, *a, **k):
-        return 64
-
-    def conv_norm_stats_floats(self, *a, **k):
-        return 64
-
-    def conv_norm_counter_words(self, *a, **k):
-        return 8
-
-    @contextlib.contextmanager
-    def conv_pair(self, enabled=True):
-        yield
-
-    def WgradGroup(self, wgs):
-        ledger = self
-
-        class Group(list):
-            def add(self, g, x, dy, dw, dbias, flops=0):
-                self.append((x, dy))
-
-            def launch(self):
-                ledger.events.append(("group", ledger.current, len(self)))
-                del self[:]
-        return Group()
-
-    def _launch(self, name, a, k):
-        idx = len(self.events)
-        out = None
-        w = WRITES.get(name)
-        if isinstance(w, str):
-            out = k.get(w)
-        elif w is not None and w < len(a):
-            out = a[w]
-        self.events.append(("launch", name, self.current))
-        if torch.is_tensor(out):
-            self.writes.append((idx, _span(out)))
-        if name in ("conv2d_fwd", "conv2d_fwd_norm"):
-            return out
-        return out
-
-    def conv2d_wgrad(self, geom, x, dy, slab, flops=0, dbias=None, acc_stride=0, cu_budget=0):
-        self.events.append(("wgrad", self.current, [dict(x=x, dy=dy, dw_slab=slab)]))
-
-    def conv2d_wgrad_list(self, calls):
-        self.events.append(("wgrad", self.current, list(calls)))
-
-
-@pytest.fixture
-def ledger(monkeypatch):
-    led = Ledger()
-    monkeypatch.setattr(engine, "ops", led)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: led.main)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-
-    @contextlib.contextmanager
-    def on(stream):
-        old, led.current = led.current, stream.name
-        try:
-            yield
-        finally:
-            led.current = old
-    monkeypatch.setattr(torch.cuda, "stream", on)
-    slab = engine.Conv.wgrad_slab
-
-    def wgrad_slab(self, g, dtype, cu_budget):
-        s = slab(self, g, dtype, cu_budget)
-        led.born[s.data_ptr()] = len(led.events)
-        return s
-    monkeypatch.setattr(engine.Conv, "wgrad_slab", wgrad_slab)
-    return led
+from walk_ledger import Stream, ledger, overlap as _overlap, span as _span  # noqa: F401  (ledger: the fixture)
 
 
 def _sweep(led, arch, value, hook=True):

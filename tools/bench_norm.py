@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(HERE, "tools"))
 import torch  # noqa: E402
 
 from kd6d import ops  # noqa: E402
+from kd6d.engine import ConvBlock  # noqa: E402
 from bench_conv import timeit_graph  # noqa: E402
 
 B = 16
@@ -55,7 +56,7 @@ def main():
         dz = torch.randn(rows, c, device=dev).to(bf)
         y = torch.empty(rows, c, dtype=bf, device=dev)
         dx = torch.empty(rows, c, dtype=bf, device=dev)
-        R = 8 if rows >= (1 << 14) else 1          # as kd6d/engine.py ConvBlock.bwd_replicas
+        R = ConvBlock.bwd_replicas(rows)
         q = bn_scratch(c, R, dev)
         gamma, beta = torch.ones(c, device=dev), torch.zeros(c, device=dev)
         rm, rv = torch.zeros(c, device=dev), torch.ones(c, device=dev)
