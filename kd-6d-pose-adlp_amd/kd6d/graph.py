@@ -22,118 +22,238 @@ to batch k-1 and `flush()` trains on the last pending batch.  The critical path 
 teacher + student to max(teacher, student), and the two halves fill each other's idle CUs.
 """
 
+import contextlib
+import math
+
 import torch
 
 from . import ops
+from .group_pipeline import GroupPipeline
 from .kd_losses import DeferredTeacher, PackedTargets
 from .libs import distributed as D
 from .libs.poses import ImageList
 
 
-class GraphedKDStep:
-    WGRAD_STREAMS = 4          # weight-gradient launches kept in flight beside the dgrad / normalisation chain
-    # ... each sized (split-K count) for CUs / this many.  Pipelined steps (a teacher forward shares the device for
-    # the first 60 % of the step): CUs / 2; strictly sequential steps: CUs / 4 (4242 against 4168 images/s).
+@contextlib.contextmanager
+def _setting(obj, **values):
+    """Attributes of `obj` set for the length of a `with`; what they held before comes back on the way out."""
+    before = {k: getattr(obj, k, None) for k in values}
+    for k, v in values.items():
+        setattr(obj, k, v)
+    try:
+        yield
+    finally:
+        for k, v in before.items():
+            setattr(obj, k, v)
+
+
+# ---- byte blocks: everything a step hands over lives in ONE uint8 tensor, so that handing it over is ONE device copy ----
+def _part_bytes(part):
+    if isinstance(part, int):
+        return part
+    shape, dtype = part
+    return math.prod(shape) * torch.empty(0, dtype=dtype).element_size()
+
+
+def block_layout(parts):
+    """parts: a byte count or a (shape, dtype) each.  -> (offsets, total bytes), every part on a 256-byte boundary."""
+    offs, total = [], 0
+    for part in parts:
+        offs.append(total)
+        total += (_part_bytes(part) + 255) // 256 * 256
+    return offs, total
+
+
+def block_views(block, parts, offs):
+    """The parts of block_layout() as views of `block` (uint8): raw bytes for a byte count, typed and shaped otherwise."""
+    views = []
+    for part, o in zip(parts, offs):
+        raw = block[o:o + _part_bytes(part)]
+        views.append(raw if isinstance(part, int) else raw.view(part[1]).view(part[0]))
+    return views
+
+
+class _KDStepBase:
+    """What both replayed steps are made of: streams and weight-gradient settings, the student's step body, the gradient
+    exchange, and THE capture and replay routines."""
+    # ... each weight-gradient launch sized (split-K count) for CUs / this many.  Pipelined steps (a teacher forward
+    # shares the device for the first 60 % of the step): CUs / 2; strictly sequential steps: CUs / 4 (4242 against 4168
+    # images/s).
     WGRAD_BUDGET_DIV = {True: 2.0, False: 4.0}
 
-    def __init__(self, teacher, student, optimizer, loss_weights=(0.1, 1.0, 5.0), cfg_kd=None, warmup=3,
-                 concurrent=True, pipeline=False, exchange=None):
+    def __init__(self, teacher, student, optimizer, loss_weights, cfg_kd, warmup, exchange, teacher_stream, side_streams,
+                 wgrad):
         self.teacher, self.student, self.opt = teacher, student, optimizer
         # fork/join inside the captured graph: the teacher's forward runs beside the student's, and the weight
         # gradients beside the dgrad / normalisation chain (many of these kernels fill < 256 CUs on their own)
-        self.teacher_stream = torch.cuda.Stream() if (concurrent or pipeline) else None
+        self.teacher_stream = torch.cuda.Stream() if teacher_stream else None
         # ... with several weight gradients in flight, each sized for a share of the CUs: the same k-loop work
         # with proportionally fewer atomic dW-tile flushes (measured: 1 -> 4 streams = +8 % on the step)
         # (WGRAD_STREAMS / WGRAD_BUDGET_DIV.  Swept on the closing state of round 1, medians of
         #  3 runs: 4 streams at CUs/4 4539 images/s, CUs/3 4566, CUs/2 4595-4640, CUs/1.5 4597, whole device 4529;
         #  3 streams 4330-4430, 5 streams 4140-4200, 6-8 streams 4340)
-        nside = self.WGRAD_STREAMS
-        budget_div = self.WGRAD_BUDGET_DIV[bool(pipeline)]
         snet = student.net
-        snet.side_stream = torch.cuda.Stream() if concurrent else None
-        snet.side_streams = ([snet.side_stream] + [torch.cuda.Stream() for _ in range(nside - 1)]
-                             if concurrent and nside > 1 else None)
-        snet.wgrad_cu_budget = int(ops.device_cu_count() / budget_div) if concurrent and nside > 1 else 0
-        # grouped head weight gradients: one workgroup per two CUs beside a teacher forward (5284-5292 images/s against
-        # 5215-5234 at one per CU and 5208-5214 at two), two per CU when the step is strictly sequential (4553 against 4467)
-        snet.wgrad_group_wgs = ops.device_cu_count() // 2 if pipeline else 2 * ops.device_cu_count()
-        snet.wgrad_group_flush = "head_end" if pipeline else "fpn_end"      # measured, see WgradSchedule.flush_group
+        snet.side_stream = torch.cuda.Stream() if side_streams else None
+        snet.side_streams = ([snet.side_stream] + [torch.cuda.Stream() for _ in range(side_streams - 1)]
+                             if side_streams > 1 else None)
+        snet.wgrad_cu_budget, snet.wgrad_group_wgs, snet.wgrad_group_flush = wgrad
         self.w_cls, self.w_reg, self.w_kd = (float(w) for w in loss_weights)
         self._w = None                                     # the same weights as a device tensor
         self.cfg_kd = cfg_kd
         self.warmup = warmup
-        self.pipeline = pipeline
         self.g_step = self.g_opt = None
         self.graphs_per_step = 2
         self.images = self.tgt = self.losses = None        # the batch the student trains on
-        self.images_nxt = self.tgt_nxt = None              # pipeline: the batch the teacher looks at
-        self.t_cur = None                                  # pipeline: teacher cells of `images`
-        self._blocks = None                                # pipeline: [current, next] hand-over blocks
-        self._nhwc = None                                  # pipeline: (current, next) packed NHWC inputs inside them
-        self.pending = False
-        self.primed = False                                # pipeline: the teacher has seen a batch the student has not
+        self.t_cur = None                                  # pipelines: teacher cells of `images`
+        self._nhwc = None                                  # pipelines: (current, next) packed NHWC inputs
         # data-parallel exchange schedule (kd6d/libs/distributed.py EXCHANGE_MODE): "between" the two graphs, or
         # "overlap" = two slices captured inside the single step graph, the big one beside the backbone sweep
         self.exchange = exchange or D.EXCHANGE_MODE
         assert self.exchange in ("between", "overlap")
-        self.comm_stream = None
-        self._split = None
+
+    @classmethod
+    def _wgrad_settings(cls, teacher_beside):
+        """(wgrad_cu_budget, wgrad_group_wgs, wgrad_group_flush) of the student's network for a step whose first part a
+        teacher forward shares the device with, or for a strictly sequential one."""
+        cus = ops.device_cu_count()
+        budget = int(cus / cls.WGRAD_BUDGET_DIV[bool(teacher_beside)])
+        # grouped head weight gradients: one workgroup per two CUs beside a teacher forward (5284-5292 images/s against
+        # 5215-5234 at one per CU and 5208-5214 at two), two per CU when the step is strictly sequential (4553 against 4467)
+        # ... and where the group goes out: measured, see WgradSchedule.flush_group
+        return (budget, cus // 2, "head_end") if teacher_beside else (budget, 2 * cus, "fpn_end")
 
     @property
-    def pending_steps(self):
-        """Batches the pipeline holds that have not had their student step yet."""
-        return int(bool(self.pipeline and self.pending and self.primed))
+    def pending(self):
+        return self.pending_steps > 0
 
-    # ---- the body the reference's loop runs per iteration (train_kd.py:104-137) ----------
     def _overlap(self):
         return self.exchange == "overlap" and D.exchange_active()
-
-    def _early_exchange(self):
-        """PoseNet.backward calls this when the FPN + head gradients have been issued: their all-reduce goes out on the
-        communication stream, behind everything the weight-gradient streams and the sweep's stream hold so far."""
-        snet = self.student.net
-        comm = self.comm_stream
-        for side in [torch.cuda.current_stream()] + snet.wgrad.streams():
-            comm.wait_stream(side)
-        with torch.cuda.stream(comm):
-            snet.store.resolve_grads(self._split, snet.store.n_train)      # accumulated FPN + head gradients -> fp32
-            D.exchange_slice(snet.store, self._split, snet.store.n_train)
 
     def _per_object(self):
         """The teacher selects its cells per (image, ground-truth slot) (PoseModuleKD.kd_per_object)."""
         return bool(getattr(self.teacher, "kd_per_object", False))
 
+    # ---- the student's half of the body the reference's loop runs per iteration (train_kd.py:104-137) ----------
     def _student_step(self, pred_t):
         if self._w is None:
             self._w = torch.tensor([self.w_cls, self.w_reg, self.w_kd], dtype=torch.float32,
                                    device=self.student.net.device)
-        snet = self.student.net
-        snet.nhwc_in = self._nhwc[0] if self._nhwc is not None else None
-        overlap = self._overlap()
-        if overlap:
-            if self.comm_stream is None:
-                self.comm_stream = torch.cuda.Stream()
-                self._split = D.bucket_split(snet.store)
-            snet.grad_hook = self._early_exchange
-            snet.resolve_hi = self._split
-        try:
+        # the exchange is this object's business: inside the sweep ("overlap", D.overlapped_exchange) or after the step
+        # (_exchange); set around the call only, an eager step of the same module keeps its own choice
+        schedule = "overlap" if self.exchange == "overlap" else "deferred"
+        with _setting(self.student.net, nhwc_in=self._nhwc[0] if self._nhwc is not None else None), \
+                _setting(self.student, exchange_schedule=schedule):
             losses = self.student.step_losses(self.images, self.tgt, pred_t, self._w)
-        finally:
-            snet.nhwc_in = None
-            snet.grad_hook = None
-            snet.resolve_hi = None
-        if overlap:        # the sweep has joined its side streams: the backbone's slice, behind the big one
-            torch.cuda.current_stream().wait_stream(self.comm_stream)
-            D.exchange_slice(snet.store, 0, self._split)
         return {"loss_cls": losses[0], "loss_reg": losses[1], "loss_kd": losses[2]}
 
+    def _exchange(self):
+        if not self._overlap():            # (overlap: both slices were issued inside the step already)
+            D.exchange_gradients(self.student.net.store)
+
+    def _count_opt_step(self):
+        # torch's lr schedulers count optimizer.step() calls to warn about ordering
+        if hasattr(self.opt, "_opt_called"):
+            self.opt._opt_called = True
+        if hasattr(self.opt, "_step_count"):
+            self.opt._step_count += 1
+
+    # ---- capture ------------------------------------------------------------------------------
+    def _snapshot(self):
+        st, opt = self.student.net.store, self.opt
+        return dict(params=st.params.clone(), bufs=st.bufs.clone(), m=opt.exp_avg.clone(), v=opt.exp_avg_sq.clone(),
+                    nbt=self.student._nbt.clone(), steps=opt.steps, sc=getattr(opt, "_step_count", None))
+
+    def _restore(self, snap):
+        st, opt = self.student.net.store, self.opt
+        st.params.copy_(snap["params"]); st.bufs.copy_(snap["bufs"])
+        opt.exp_avg.copy_(snap["m"]); opt.exp_avg_sq.copy_(snap["v"])
+        self.student._nbt.copy_(snap["nbt"])
+        if st.shadow is not None:
+            st.refresh_shadow()                 # bf16 copy of the restored master weights
+        opt.steps = snap["steps"]
+        if snap["sc"] is not None:
+            opt._step_count = snap["sc"]
+
+    def _capture_graphs(self, bodies, warmup_exchange):
+        """One graph per step body (all in one pool) [+ the optimiser's], the training state as it was -> the graphs.
+        warmup_exchange: the eager warm-up steps run the gradient exchange too."""
+        snap = self._snapshot()                              # the warm-up steps below must not train
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                        # eager warm-up: allocates every static buffer
+            for _ in range(self.warmup):
+                for body in bodies:
+                    body()
+                    if warmup_exchange:
+                        self._exchange()
+                    self.opt.advance()
+                    self.opt.launch(device_schedule=True)
+                    self._count_opt_step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        # Without a gradient exchange (one rank) nothing has to happen between the reverse sweep and the optimiser:
+        # ONE graph per step, and the eager kd6d_set_hyper launch moves in front of it.  With an exchange the RCCL
+        # all-reduce sits between two graphs.
+        self.graphs_per_step = 2 if (D.exchange_active() and not self._overlap()) else 1
+        graphs, pool = [], None
+        for body in bodies:
+            g = torch.cuda.CUDAGraph()
+            # thread-local capture mode: with a process group alive, RCCL's watchdog thread polls events concurrently
+            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+                self.losses = body()
+                if self.graphs_per_step == 1:
+                    self.opt.launch(device_schedule=True)
+            pool = g.pool()
+            graphs.append(g)
+        if self.graphs_per_step == 2:
+            self.g_opt = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_opt, pool=pool, capture_error_mode="thread_local"):
+                self.opt.launch(device_schedule=True)
+        self._restore(snap)
+        return graphs
+
+    def _replay(self, graph):
+        """One training step from its graph: the ONE place that knows the order."""
+        if self.graphs_per_step == 1:
+            self.opt.advance()                 # lr / bias corrections of THIS step, consumed at the graph's end
+            graph.replay()
+        else:
+            graph.replay()
+            self._exchange()
+            self.opt.advance()
+            self.g_opt.replay()
+        self._count_opt_step()
+        for _, bn in self.student.net.bns:     # what FusedClipAdamW.launch() does when it runs from Python: the
+            bn.fold = None                     # cached eval-mode BN scale/shift belong to the previous weights
+        return self.losses
+
+
+class GraphedKDStep(_KDStepBase):
+    WGRAD_STREAMS = 4          # weight-gradient launches kept in flight beside the dgrad / normalisation chain
+    # (one knob for both step classes: the grouped step reads it here too)
+
+    def __init__(self, teacher, student, optimizer, loss_weights=(0.1, 1.0, 5.0), cfg_kd=None, warmup=3,
+                 concurrent=True, pipeline=False, exchange=None):
+        nside = self.WGRAD_STREAMS if concurrent else 0
+        budget, wgs, flush = self._wgrad_settings(pipeline)
+        super().__init__(teacher, student, optimizer, loss_weights, cfg_kd, warmup, exchange,
+                         teacher_stream=concurrent or pipeline, side_streams=nside,
+                         wgrad=(budget if nside > 1 else 0, wgs, flush))
+        self.pipeline = pipeline
+        self.images_nxt = self.tgt_nxt = None              # pipeline: the batch the teacher looks at
+        self._blocks = None                                # pipeline: [current, next] hand-over blocks
+        self.primed = False                                # pipeline: the teacher has seen a batch the student has not
+
+    @property
+    def pending_steps(self):
+        """Batches the pipeline holds that have not had their student step yet."""
+        return int(self.primed)
+
+    # ---- the body the reference's loop runs per iteration (train_kd.py:104-137) ----------
     def _teacher(self, images, tgt):
-        tnet = self.teacher.net
-        tnet.nhwc_out = self._nhwc[1] if (self._nhwc is not None and images is self.images_nxt) else None
-        try:
+        out = self._nhwc[1] if (self._nhwc is not None and images is self.images_nxt) else None
+        with _setting(self.teacher.net, nhwc_out=out):
             return self._teacher_launch(images, tgt)
-        finally:
-            tnet.nhwc_out = None
 
     def _teacher_launch(self, images, tgt):
         with torch.no_grad():
@@ -180,18 +300,10 @@ class GraphedKDStep:
         snet, tnet = self.student.net, self.teacher.net
         assert snet.dtype == tnet.dtype, "teacher and student share the converted input: same precision"
         nhwc_cur = ops.image_to_nhwc(self.images.tensors, snet.dtype, 8)
-        tgt_bytes = torch.empty(self.tgt.block_bytes(), dtype=torch.uint8, device=dev)      # shape donor only
-        parts = [nhwc_cur, tgt_bytes, self.t_cur.flats[0], self.t_cur.flats[1]]
-        offs, total = [], 0
-        for t in parts:
-            offs.append(total)
-            total += (t.numel() * t.element_size() + 255) // 256 * 256
+        parts = [(nhwc_cur.shape, nhwc_cur.dtype), self.tgt.block_bytes()] + [(f.shape, f.dtype) for f in self.t_cur.flats]
+        offs, total = block_layout(parts)
         blocks = [torch.zeros(total, dtype=torch.uint8, device=dev) for _ in range(2)]
-
-        def views(block):
-            return [block[o:o + t.numel() * t.element_size()].view(t.dtype).view(t.shape) for o, t in zip(offs, parts)]
-
-        cur, nxt = views(blocks[0]), views(blocks[1])
+        cur, nxt = (block_views(b, parts, offs) for b in blocks)
         cur[0].copy_(nhwc_cur)
         ops.image_to_nhwc(self.images_nxt.tensors, snet.dtype, 8, out=nxt[0])
         self._nhwc = (cur[0], nxt[0])
@@ -218,92 +330,23 @@ class GraphedKDStep:
         dst_t.copy_from(tgt)
 
     # ---- capture ------------------------------------------------------------------------------
-    def _snapshot(self):
-        st, opt = self.student.net.store, self.opt
-        snap = dict(params=st.params.clone(), bufs=st.bufs.clone(), m=opt.exp_avg.clone(), v=opt.exp_avg_sq.clone(),
-                    nbt=self.student._nbt.clone(), steps=opt.steps, sc=getattr(opt, "_step_count", None))
-        if self.pipeline:
-            snap.update(img=(self._nhwc[0] if self._nhwc is not None else self.images.tensors).clone(),
-                        mask=self.tgt.mask.clone(), ff=self.tgt.flat_f.clone(),
-                        fi=self.tgt.flat_i.clone(), tf=self.t_cur.flats[0].clone(), ti=self.t_cur.flats[1].clone())
-        return snap
-
-    def _restore(self, snap):
-        st, opt = self.student.net.store, self.opt
-        st.params.copy_(snap["params"]); st.bufs.copy_(snap["bufs"])
-        opt.exp_avg.copy_(snap["m"]); opt.exp_avg_sq.copy_(snap["v"])
-        self.student._nbt.copy_(snap["nbt"])
-        if st.shadow is not None:
-            st.refresh_shadow()                 # bf16 copy of the restored master weights
-        opt.steps = snap["steps"]
-        if snap["sc"] is not None:
-            opt._step_count = snap["sc"]
-        if self.pipeline:                       # the warm-up iterations advanced the pipeline: rewind it
-            (self._nhwc[0] if self._nhwc is not None else self.images.tensors).copy_(snap["img"])
-            self.tgt.mask.copy_(snap["mask"])
-            self.tgt.flat_f.copy_(snap["ff"]); self.tgt.flat_i.copy_(snap["fi"])
-            self.t_cur.flats[0].copy_(snap["tf"]); self.t_cur.flats[1].copy_(snap["ti"])
+    def _handover(self):
+        """pipeline=True: what the student reads of the hand-over (image, targets, teacher cells).  The warm-up
+        iterations of a capture advance the pipeline; these are what rewinds it."""
+        img = self._nhwc[0] if self._nhwc is not None else self.images.tensors
+        return [img, self.tgt.mask, self.tgt.flat_f, self.tgt.flat_i, self.t_cur.flats[0], self.t_cur.flats[1]]
 
     def _capture(self):
-        self.student._defer_allreduce = True
         if self.pipeline and self._blocks is None:
             self._make_blocks()
         elif not self.pipeline and getattr(self.teacher, "_teacher_flats", None) is None:
             from .kd_losses import teacher_flats     # caller-owned teacher outputs: cleared by the teacher's prologue
             self.teacher._teacher_flats = teacher_flats(self.images.tensors.shape[0], self.images.tensors.device,
                                                         per_object=self._per_object())
-        snap = self._snapshot()                              # the warm-up steps below must not train
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # eager warm-up: allocates every static buffer
-            for _ in range(self.warmup):
-                self._forward_backward()
-                self._exchange()
-                self.opt.advance()
-                self.opt.launch(device_schedule=True)
-                self._count_opt_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        # Without a gradient exchange (one rank) nothing has to happen between the reverse sweep and the optimiser:
-        # ONE graph per step, and the eager kd6d_set_hyper launch moves in front of it.  With an exchange the RCCL
-        # all-reduce sits between two graphs.
-        self.graphs_per_step = 2 if (D.exchange_active() and not self._overlap()) else 1
-        self.g_step = torch.cuda.CUDAGraph()
-        # thread-local capture mode: with a process group alive, RCCL's watchdog thread polls events concurrently
-        with torch.cuda.graph(self.g_step, capture_error_mode="thread_local"):
-            self.losses = self._forward_backward()
-            if self.graphs_per_step == 1:
-                self.opt.launch(device_schedule=True)
-        if self.graphs_per_step == 2:
-            self.g_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_opt, pool=self.g_step.pool(), capture_error_mode="thread_local"):
-                self.opt.launch(device_schedule=True)
-        self._restore(snap)
-
-    def _exchange(self):
-        if not self._overlap():            # (overlap: both slices were issued inside the step already)
-            D.exchange_gradients(self.student.net.store)
-
-    def _count_opt_step(self):
-        # torch's lr schedulers count optimizer.step() calls to warn about ordering
-        if hasattr(self.opt, "_opt_called"):
-            self.opt._opt_called = True
-        if hasattr(self.opt, "_step_count"):
-            self.opt._step_count += 1
-
-    def _replay(self):
-        if self.graphs_per_step == 1:
-            self.opt.advance()                 # lr / bias corrections of THIS step, consumed at the graph's end
-            self.g_step.replay()
-        else:
-            self.g_step.replay()
-            self._exchange()
-            self.opt.advance()
-            self.g_opt.replay()
-        self._count_opt_step()
-        for _, bn in self.student.net.bns:     # what FusedClipAdamW.launch() does when it runs from Python: the
-            bn.fold = None                     # cached eval-mode BN scale/shift belong to the previous weights
-        return self.losses
+        kept = [(t, t.clone()) for t in self._handover()] if self.pipeline else []
+        self.g_step, = self._capture_graphs([self._forward_backward], warmup_exchange=True)
+        for t, before in kept:
+            t.copy_(before)
 
     # ---- public -------------------------------------------------------------------------------
     def __call__(self, images, tgt):
@@ -312,16 +355,10 @@ class GraphedKDStep:
         if not isinstance(tgt, PackedTargets):
             tgt = PackedTargets(tgt, self.student.net.device)
         self._load(images, tgt)
-        if not self.pipeline:
-            if self.g_step is None:
-                self._capture()
-            return self._replay()
-        if not self.primed:                     # priming call: teacher only, the student starts next call
-            flats = getattr(self.teacher, "_teacher_flats", None)
-            self.teacher._teacher_flats = None  # (eager call: fresh output buffers, not the captured step's)
-            with torch.no_grad():
+        if self.pipeline and not self.primed:   # priming call: teacher only, the student starts next call
+            # (eager call: fresh output buffers, not the captured step's)
+            with _setting(self.teacher, _teacher_flats=None), torch.no_grad():
                 pred = self.teacher(self.images_nxt, targets=self.tgt_nxt, is_teacher=True, cfg_kd=self.cfg_kd)
-            self.teacher._teacher_flats = flats
             if self.t_cur is None:
                 self.t_cur = pred.clone_static()
             else:                               # a new pipeline after flush(): the captured step's buffers stay
@@ -330,21 +367,19 @@ class GraphedKDStep:
             if self._nhwc is not None:
                 ops.image_to_nhwc(self.images_nxt.tensors, self.student.net.dtype, 8, out=self._nhwc[0])
             self.tgt.copy_from(self.tgt_nxt)
-            self.primed = self.pending = True
+            self.primed = True
             return None
         if self.g_step is None:
             self._capture()
-        self.pending = True
-        return self._replay()
+        return self._replay(self.g_step)
 
     def flush(self):
         """pipeline=True: train on the batch that is still waiting for its student step."""
-        if not (self.pipeline and self.pending and self.primed):
+        if not self.primed:
             return None
         if self.g_step is None:
             self._capture()
-        self.pending = False
-        out = self._replay()       # the teacher re-reads the same (last) batch: harmless, results unused
+        out = self._replay(self.g_step)    # the teacher re-reads the same (last) batch: harmless, results unused
         self.primed = False        # a later call starts a new pipeline (teacher only) instead of repeating this batch
         return out
 
@@ -355,7 +390,7 @@ class _GroupSide:
     __slots__ = ("block", "nhwc", "tgts", "wf", "wi", "tk")
 
 
-class GroupedTeacherKDStep(GraphedKDStep):
+class GroupedTeacherKDStep(_KDStepBase):
     """The pipelined step with the frozen teacher run over the batches of `group` consecutive steps AT ONCE, its pass
     cut into `group` segments of equal device time, one beside every student step.
 
@@ -364,15 +399,13 @@ class GroupedTeacherKDStep(GraphedKDStep):
     the head towers, 8-32 tiles in stages 4-5), and the same forward over 32 / 48 images costs 83 / 72 us per image
     instead of 104 (tools/teacher_batch_probe.py).
 
-    Three blocks of `group` batches each: LOAD (being filled, one batch per call), PASS (the teacher's input and, once
-    its last segment has run, its cells) and CURRENT (what the student trains on).  Call k = m * group + s
-        converts batch k into slot s of LOAD,
-        replays teacher segment s (its own hipGraph, on the teacher's stream) over PASS = the batches of period m - 1,
-        replays student step s (its own hipGraph [+ the optimiser]) on slot s of CURRENT = batch k - 2 * group,
-    and the last call of a period ends with CURRENT <- PASS <- LOAD (two device copies, both streams joined).  Every
-    batch still gets exactly one teacher forward and one student step.  The losses a call returns belong to batch
-    k - 2 * group (None for the first 2 * group calls); `flush()` trains one pending batch per call without consuming a
-    new one.  The teacher's segments are cut where a timed trial replay (device timestamps at every layer-group
+    Which batch sits in which of the three blocks (LOAD, PASS, CURRENT) and what a call issues is `GroupPipeline`'s
+    business (kd6d/group_pipeline.py: its docstring states the rules); this class is the device side of it.  Loading a
+    batch converts it into its slot of LOAD; a teacher segment is a hipGraph of its own, replayed on the teacher's
+    stream; a student step is a hipGraph of its own [+ the optimiser's]; a rotation is two device copies with both
+    streams joined.  The losses a call returns belong to batch k - 2 * group (None for the first 2 * group calls);
+    `flush()` trains one pending batch per call without consuming a new one.
+    The teacher's segments are cut where a timed trial replay (device timestamps at every layer-group
     boundary, PoseNet.cut_hook) says the pass has spent s / group of its time; the cut graphs are captured in ONE walk
     through the forward, ending one capture and beginning the next at those boundaries.
 
@@ -389,44 +422,31 @@ class GroupedTeacherKDStep(GraphedKDStep):
                  exchange=None):
         if int(group) < 2:
             raise ValueError("GroupedTeacherKDStep: group >= 2 (GraphedKDStep(pipeline=True) is the group of one)")
-        super().__init__(teacher, student, optimizer, loss_weights, cfg_kd=cfg_kd, warmup=warmup, concurrent=True,
-                         pipeline=True, exchange=exchange)
-        self.group = int(group)
         # the student's graphs have no teacher branch of their own and the teacher's segments run beside ALL of a step,
         # not its first 60 %: the weight-gradient settings of the strictly sequential step win here too (100-step runs,
         # interleaved, group 2: 5950-5980 images/s with the pipelined settings, 6200-6220 with two workgroups per CU for
         # the grouped launch and its flush behind the FPN sweep; CUs / 4 per side-stream launch: +-0)
-        snet = student.net
-        snet.wgrad_cu_budget = int(ops.device_cu_count() / self.WGRAD_BUDGET_DIV[False])
-        snet.wgrad_group_wgs = 2 * ops.device_cu_count()
-        snet.wgrad_group_flush = "fpn_end"
+        super().__init__(teacher, student, optimizer, loss_weights, cfg_kd, warmup, exchange, teacher_stream=True,
+                         side_streams=GraphedKDStep.WGRAD_STREAMS, wgrad=self._wgrad_settings(False))
+        self.group = int(group)
+        self.pipeline = True
+        self.pipe = GroupPipeline(self.group, self)       # which batch is where, what a call issues
         self.g_student = self.g_teacher = None
         self._debug_skip_teacher = 0      # timing experiments only (bench.py --debug-skip-teacher): 1 = no teacher segment
         # is replayed, 2 = every second one
         self.sides = None                 # [current, pass, load]
-        self.n_loaded = 0                 # batches in the load block
-        self.p_valid = 0                  # batches of the pass block (the teacher's input)
-        self.t_pos = 0                    # next teacher segment of the pass block
-        self.c_valid = 0                  # batches of the current block (they carry teacher cells)
-        self.c_pos = 0                    # next slot of the current block to train on
-        self.draining = False
         self._img_big = self._tgt_big = None
         self._geom = None
-        self.teacher_passes = 0           # completed group passes (bench.py reports them)
         self.segment_ms = None            # the trial replay's time per segment
 
-    # `pending` of the base class, as a count
     @property
     def pending_steps(self):
-        return (self.c_valid - self.c_pos) + self.p_valid + self.n_loaded
+        return self.pipe.pending_steps
 
     @property
-    def pending(self):
-        return self.pending_steps > 0
-
-    @pending.setter
-    def pending(self, value):
-        pass
+    def teacher_passes(self):
+        """Completed group passes (bench.py reports them)."""
+        return self.pipe.teacher_passes
 
     # ---- blocks ---------------------------------------------------------------------------------
     def _build_sides(self, x, tgt):
@@ -442,34 +462,24 @@ class GroupedTeacherKDStep(GraphedKDStep):
         dev = x.device
         snet, tnet = self.student.net, self.teacher.net
         assert snet.dtype == tnet.dtype, "teacher and student share the converted input: same precision"
-        esz = torch.empty((), dtype=snet.dtype).element_size()
-        img_b = B * H * W * 8 * esz
-        tb = tgt.block_bytes()
         per_object = self._per_object()
         wf_n, wi_n = teacher_flat_sizes(T * B, CAP, per_object)      # one selection over the group's T * B images
-        wf_b = wf_n * 4
-
-        def al(v):
-            return (v + 255) // 256 * 256
-
-        o_tgt = al(T * img_b)
-        o_wf = o_tgt + T * al(tb)
-        o_wi = o_wf + al(wf_b)
-        total = o_wi + al(wi_n * 4)
+        # the group's images, a target block per slot, the two buffers of the teacher's cells
+        parts = ([((T * B * H * W, 8), snet.dtype)] + [tgt.block_bytes()] * T
+                 + [((wf_n,), torch.float32), ((wi_n,), torch.int32)])
+        offs, total = block_layout(parts)
         sides = []
         for _ in range(3):
             sd = _GroupSide()
-            blk = sd.block = torch.zeros(total, dtype=torch.uint8, device=dev)
-            sd.nhwc = blk[0:T * img_b].view(snet.dtype).view(T * B * H * W, 8)
+            sd.block = torch.zeros(total, dtype=torch.uint8, device=dev)
+            sd.nhwc, *tgt_bytes, sd.wf, sd.wi = block_views(sd.block, parts, offs)
             sd.tgts = []
-            for s in range(T):
+            for raw in tgt_bytes:
                 t = tgt.clone_static()
-                t.rebind_block(blk[o_tgt + s * al(tb):o_tgt + s * al(tb) + tb])
+                t.rebind_block(raw)
                 sd.tgts.append(t)
-            wf = sd.wf = blk[o_wf:o_wf + wf_b].view(torch.float32)
-            wi = sd.wi = blk[o_wi:o_wi + wi_n * 4].view(torch.int32)
             # the cells of slot s: a contiguous range of every slot array (they are image-major), no copies
-            sd.tk = TeacherKnowledge.group_views(wf, wi, T, B, CAP, per_object)
+            sd.tk = TeacherKnowledge.group_views(sd.wf, sd.wi, T, B, CAP, per_object)
             sides.append(sd)
         self.sides = sides
         self._geom = (B, H, W)
@@ -497,12 +507,8 @@ class GroupedTeacherKDStep(GraphedKDStep):
         B, H, W = self._geom
         return slice(s * B * H * W, (s + 1) * B * H * W)
 
-    def _load_group(self, images, tgt):
-        assert self.n_loaded < self.group
-        self._load_device(images, tgt, self.n_loaded)
-        self.n_loaded += 1
-
-    def _load_device(self, images, tgt, s):
+    # ---- GroupPipeline's interface: the blocks ---------------------------------------------------
+    def load_slot(self, s, images, tgt):
         x = images.tensors if hasattr(images, "tensors") else images
         B, H, W = self._geom
         assert tuple(x.shape) == (B, 3, H, W), "the captured step has a static batch shape"
@@ -513,25 +519,14 @@ class GroupedTeacherKDStep(GraphedKDStep):
         ops.image_to_nhwc(x.contiguous(), self.student.net.dtype, 8, out=L.nhwc[self._slot_rows(s)])
         L.tgts[s].copy_from(tgt)
 
-    def _fill_unloaded(self):
-        """A partial load block (a drain before `group` batches arrived): the free slots repeat slot 0, so that the
-        group pass and a capture's warm-up steps see valid inputs everywhere."""
-        L = self.sides[2]
-        for s in range(self.n_loaded, self.group):
-            L.nhwc[self._slot_rows(s)].copy_(L.nhwc[self._slot_rows(0)], non_blocking=True)
-            L.tgts[s].copy_from(L.tgts[0])
-
-    def _rotate(self):
-        """Period end: CURRENT <- PASS <- LOAD.  The caller has issued every teacher segment of the pass block."""
-        self._rotate_device(bool(self.p_valid), self.n_loaded)
-        self.c_valid, self.p_valid, self.n_loaded = self.p_valid, self.n_loaded, 0
-        self.c_pos = self.t_pos = 0
-
-    def _rotate_device(self, pass_valid, n_loaded):
+    def rotate_blocks(self, pass_valid, n_loaded):
         main, ts = torch.cuda.current_stream(), self.teacher_stream
         C, P, L = self.sides
-        if 0 < n_loaded < self.group:
-            self._fill_unloaded()
+        # a partial load block (a drain before `group` batches arrived): the free slots repeat slot 0, so that the
+        # group pass and a capture's warm-up steps see valid inputs everywhere
+        for s in range(n_loaded, self.group) if n_loaded else ():
+            L.nhwc[self._slot_rows(s)].copy_(L.nhwc[self._slot_rows(0)], non_blocking=True)
+            L.tgts[s].copy_from(L.tgts[0])
         main.wait_stream(ts)
         if pass_valid:
             C.block.copy_(P.block, non_blocking=True)
@@ -555,14 +550,8 @@ class GroupedTeacherKDStep(GraphedKDStep):
             if gate:
                 self._tgt_big.K[s * B:(s + 1) * B].copy_(P.tgts[s].K, non_blocking=True)
                 self._tgt_big.kp3d[s * B:(s + 1) * B].copy_(P.tgts[s].kp3d, non_blocking=True)
-        tnet.nhwc_in = P.nhwc
-        keep = getattr(self.teacher, "_teacher_flats", None)
-        self.teacher._teacher_flats = (P.wf, P.wi)
-        try:
+        with _setting(tnet, nhwc_in=P.nhwc), _setting(self.teacher, _teacher_flats=(P.wf, P.wi)):
             self.teacher(self._img_big, targets=self._tgt_big, is_teacher=True, cfg_kd=self.cfg_kd)
-        finally:
-            tnet.nhwc_in = None
-            self.teacher._teacher_flats = keep
         ops.mark("teacher.end")
 
     def _time_cuts(self):
@@ -585,11 +574,8 @@ class GroupedTeacherKDStep(GraphedKDStep):
             trial = torch.cuda.CUDAGraph()
             with torch.cuda.graph(trial, stream=ts, capture_error_mode="thread_local"):
                 stamp()
-                tnet.cut_hook = stamp
-                try:
+                with _setting(tnet, cut_hook=stamp):
                     self._teacher_forward()
-                finally:
-                    tnet.cut_hook = None
                 stamp()
             trial.replay(); trial.replay()
             ts.synchronize()
@@ -628,25 +614,16 @@ class GroupedTeacherKDStep(GraphedKDStep):
         torch.cuda.synchronize()
         with torch.no_grad(), torch.cuda.stream(ts):
             graphs[0].capture_begin(pool=pool, capture_error_mode="thread_local")
-            tnet.cut_hook = switch
             try:
-                self._teacher_forward()
+                with _setting(tnet, cut_hook=switch):
+                    self._teacher_forward()
             finally:
-                tnet.cut_hook = None
                 graphs[state["g"]].capture_end()
         assert state["g"] == T - 1, "the teacher's forward passed fewer cut points than segments"
         torch.cuda.synchronize()
         self.g_teacher = graphs
 
-    def _teacher_segments(self, upto):
-        """Issue the pass block's segments t_pos .. upto - 1 on the teacher's stream."""
-        while self.p_valid and self.t_pos < upto:
-            self._replay_teacher_segment(self.t_pos)
-            self.t_pos += 1
-            if self.t_pos == self.group:
-                self.teacher_passes += 1
-
-    def _replay_teacher_segment(self, i):
+    def replay_teacher_segment(self, i):
         if self.g_teacher is None:
             self._capture_teacher()
         if self._debug_skip_teacher == 1 or (self._debug_skip_teacher == 2 and i % 2 == 1):
@@ -664,108 +641,25 @@ class GroupedTeacherKDStep(GraphedKDStep):
         ops.mark("step.end")
         return losses
 
-    def _snapshot(self):
-        st, opt = self.student.net.store, self.opt
-        return dict(params=st.params.clone(), bufs=st.bufs.clone(), m=opt.exp_avg.clone(), v=opt.exp_avg_sq.clone(),
-                    nbt=self.student._nbt.clone(), steps=opt.steps, sc=getattr(opt, "_step_count", None))
-
-    def _restore(self, snap):
-        st, opt = self.student.net.store, self.opt
-        st.params.copy_(snap["params"]); st.bufs.copy_(snap["bufs"])
-        opt.exp_avg.copy_(snap["m"]); opt.exp_avg_sq.copy_(snap["v"])
-        self.student._nbt.copy_(snap["nbt"])
-        if st.shadow is not None:
-            st.refresh_shadow()
-        opt.steps = snap["steps"]
-        if snap["sc"] is not None:
-            opt._step_count = snap["sc"]
-
-    def _capture(self):
+    def ensure_captured(self):
         """The `group` student graphs (one per slot of the current block; the blocks are only read)."""
-        T = self.group
-        self.student._defer_allreduce = True
+        if self.g_student is not None:
+            return
         torch.cuda.synchronize()
-        snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                        # eager warm-up: allocates every static buffer
-            for _ in range(self.warmup):
-                for s in range(T):
-                    self._student_body(s)
-                    # (no gradient exchange here: these steps are thrown away with the snapshot, and no RCCL communicator
-                    #  may come to life before the graphs exist -- see prepare())
-                    self.opt.advance()
-                    self.opt.launch(device_schedule=True)
-                    self._count_opt_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graphs_per_step = 2 if (D.exchange_active() and not self._overlap()) else 1
-        self.g_student, pool = [], None
-        for s in range(T):
-            g = torch.cuda.CUDAGraph()
-            kw = {} if pool is None else {"pool": pool}
-            with torch.cuda.graph(g, capture_error_mode="thread_local", **kw):
-                self.losses = self._student_body(s)
-                if self.graphs_per_step == 1:
-                    self.opt.launch(device_schedule=True)
-            pool = g.pool()
-            self.g_student.append(g)
+        # (no gradient exchange in the warm-up: these steps are thrown away with the snapshot, and no RCCL communicator
+        #  may come to life before the graphs exist -- see prepare())
+        bodies = [lambda s=s: self._student_body(s) for s in range(self.group)]
+        self.g_student = self._capture_graphs(bodies, warmup_exchange=False)
         self.g_step = self.g_student[0]
-        if self.graphs_per_step == 2:
-            self.g_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_opt, pool=pool, capture_error_mode="thread_local"):
-                self.opt.launch(device_schedule=True)
-        self._restore(snap)
 
-    def _ensure_captured(self):
-        if self.g_student is None:
-            self._capture()
-
-    def _replay_student(self, s):
-        if self.graphs_per_step == 1:
-            self.opt.advance()
-            self.g_student[s].replay()
-        else:
-            self.g_student[s].replay()
-            self._exchange()
-            self.opt.advance()
-            self.g_opt.replay()
-        self._count_opt_step()
-        for _, bn in self.student.net.bns:
-            bn.fold = None
-        return self.losses
-
-    # ---- one tick of the pipeline -------------------------------------------------------------------------
-    def _tick(self, drain):
-        T = self.group
-        if drain:
-            while self.c_pos >= self.c_valid:      # nothing trainable: finish the teacher on the pass block, rotate
-                self._teacher_segments(T)
-                self._rotate()
-        out = None
-        if self.c_pos < self.c_valid:
-            s = self.c_pos
-            self._ensure_captured()                # (before this step's teacher segment goes out)
-            self._teacher_segments(s + 1)          # segment s beside student step s
-            out = self._replay_student(s)
-            self.c_pos += 1
-        if not drain and self.n_loaded == T:       # period end
-            self._teacher_segments(T)
-            self._rotate()
-        return out
+    def replay_student(self, s):
+        return self._replay(self.g_student[s])
 
     # ---- public -------------------------------------------------------------------------------------
     def __call__(self, images, tgt):
         """One call = one batch in.  Returns the (device, static) loss scalars of batch k - 2 * group, None while the
         pipeline fills (the first 2 * group calls)."""
-        tgt = self._prepare(images, tgt)
-        if self.draining:
-            if self.pending_steps > 0:
-                raise RuntimeError("GroupedTeacherKDStep: flush() the %d pending batches before feeding new ones"
-                                   % self.pending_steps)
-            self.draining = False
-        self._load_group(images, tgt)
-        return self._tick(False)
+        return self.pipe.feed(images, self._prepare(images, tgt))
 
     def _prepare(self, images, tgt):
         if not isinstance(tgt, PackedTargets):
@@ -788,22 +682,10 @@ class GroupedTeacherKDStep(GraphedKDStep):
         tgt = self._prepare(images, tgt)
         if self.g_student is not None and self.g_teacher is not None:
             return
-        if self.pending_steps:
-            raise RuntimeError("GroupedTeacherKDStep.prepare(): call it before the first batch is fed")
-        for _ in range(self.group):
-            self._load_group(images, tgt)
-        self._rotate()                          # PASS <- LOAD
-        self._teacher_segments(self.group)      # records the teacher's graphs (and runs them once: cells of the sample)
-        self._rotate()                          # CURRENT <- PASS
-        self._ensure_captured()                 # the student's graphs; snapshot / restore around their warm-up steps
+        self.pipe.prime(images, tgt)
         torch.cuda.synchronize()
-        self.n_loaded = self.p_valid = self.t_pos = self.c_valid = self.c_pos = 0
-        self.teacher_passes = 0
 
     def flush(self):
         """Train on ONE batch that is still waiting for its student step, without consuming a new one; None when
         nothing is pending.  (Call until it returns None to drain the pipeline; a later __call__ starts a new one.)"""
-        if self.pending_steps == 0:
-            return None
-        self.draining = True
-        return self._tick(True)
+        return self.pipe.flush()

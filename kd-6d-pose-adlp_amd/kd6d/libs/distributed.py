@@ -8,6 +8,7 @@ this library owns on librccl, include/kd6d.h), enqueued on the step's HIP stream
 replayed graphs; torch.distributed is only the rendezvous (the 128-byte RCCL id travels over its
 store) and the fall-back route for CPU tensors (the gloo tests) or when librccl cannot be opened.
 """
+import contextlib
 import ctypes
 import math
 
@@ -176,6 +177,32 @@ def exchange_slice(store, lo, hi):
     """Mean over ranks of grads[lo:hi] (asynchronous on the current stream)."""
     if exchange_active() and hi > lo:
         allreduce_mean_(store.grads[lo:hi])
+
+
+@contextlib.contextmanager
+def overlapped_exchange(net, comm, split):
+    """The "overlap" schedule around `net.backward(...)`, eager or under capture: inside the `with`, PoseNet.backward calls
+    the hook when the FPN + head gradients [split, n_train) have been issued -- their all-reduce goes out on the
+    communication stream `comm`, behind everything the sweep's stream and the weight-gradient streams hold so far -- and
+    resolves only [0, split) at its end; on leaving, the backbone's slice follows behind the big one."""
+    st = net.store
+
+    def early():
+        for side in [torch.cuda.current_stream()] + net.wgrad.streams():
+            comm.wait_stream(side)
+        with torch.cuda.stream(comm):
+            st.resolve_grads(split, st.n_train)      # the accumulated FPN + head gradients -> fp32 first
+            exchange_slice(st, split, st.n_train)
+
+    net.grad_hook = early
+    net.resolve_hi = split
+    try:
+        yield
+    finally:
+        net.grad_hook = None
+        net.resolve_hi = None
+    torch.cuda.current_stream().wait_stream(comm)    # the sweep has joined its side streams
+    exchange_slice(st, 0, split)
 
 
 def exchange_gradients(store):

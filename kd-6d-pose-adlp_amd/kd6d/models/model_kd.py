@@ -86,6 +86,11 @@ class PoseModuleKD(nn.Module):
         self.kd_per_object = bool(kd.get("PER_OBJECT", False))
         if self.kd_per_object and self.teacher_pnp_gate:
             raise ValueError(kd_losses.PER_OBJECT_GATE_ERROR)
+        # how the training step exchanges its gradients between ranks: None = its own choice (D.EXCHANGE_MODE, eager
+        # runs); "deferred" = not at all, the caller runs the exchange after the step; "overlap" = inside the reverse
+        # sweep (D.overlapped_exchange).  The graphed steps of kd6d.graph set it around their own calls only.
+        self.exchange_schedule = None
+        self._comm_stream = None
         self.loss_evaluator = KDLoss(cfg["INPUT"]["INTERNAL_K"], cfg["DATASETS"]["MESH_DIAMETERS"],
                                      cfg["SOLVER"]["FOCAL_GAMMA"], cfg["SOLVER"]["FOCAL_ALPHA"], self.positive_num,
                                      self.positive_lambda,
@@ -351,28 +356,15 @@ class PoseModuleKD(nn.Module):
                                      acc_stride=st.acc_stride)
         ops.mark("student.bwd.start")
         from ..libs import distributed as D
-        own = not getattr(self, "_defer_allreduce", False)      # GraphedKDStep schedules the exchange itself
-        split = D.bucket_split(st) if (own and D.exchange_active() and D.EXCHANGE_MODE == "overlap") else None
-        if split is not None:
-            comm = self._comm_stream = getattr(self, "_comm_stream", None) or torch.cuda.Stream()
-
-            def early():
-                for side in [torch.cuda.current_stream()] + net.wgrad.streams():
-                    comm.wait_stream(side)
-                with torch.cuda.stream(comm):
-                    st.resolve_grads(split, st.n_train)      # the accumulated FPN + head gradients -> fp32 first
-                    D.exchange_slice(st, split, st.n_train)
-            net.grad_hook = early
-            net.resolve_hi = split
-        try:
-            net.backward(dcls, dreg)
-        finally:
-            if split is not None:
-                net.grad_hook = None
-                net.resolve_hi = None
+        schedule = self.exchange_schedule or D.EXCHANGE_MODE       # "between" | "overlap" | "deferred"
+        if schedule == "overlap" and D.exchange_active():
+            if self._comm_stream is None:
+                self._comm_stream = torch.cuda.Stream()
+            with D.overlapped_exchange(net, self._comm_stream, D.bucket_split(st)):
+                net.backward(dcls, dreg)
+                ops.mark("student.bwd.end")
+            return
+        net.backward(dcls, dreg)
         ops.mark("student.bwd.end")
-        if split is not None:
-            torch.cuda.current_stream().wait_stream(self._comm_stream)
-            D.exchange_slice(st, 0, split)
-        elif own:
+        if schedule == "between":
             D.exchange_gradients(st)

@@ -17,7 +17,8 @@ to the layer:
 Every fork -- a list, a single layer, the group -- takes the NEXT of the side streams, round-robin.  The tail: from the
 tape index tail_start() gives, the last WGRAD_LIST_TAIL_BLOCKS blocks of the backbone sweep, enter_tail() flushes and
 every layer forks alone again (a list launched behind the last chain kernel would run with nothing beside it).  The
-caller flushes the list before its grad_hook, and finish() flushes what is left and joins every side stream once.
+caller flushes the list before its grad_hook (installed by kd6d.libs.distributed.overlapped_exchange, which waits on
+streams() there), and finish() flushes what is left and joins every side stream once.
 
 The per-layer call is built when the layer is reached (its slab, Conv.wgrad_slab, is taken then, not at the flush): a
 pending call reads x and dy later than the sweep reached the layer, which the sweep never writes again.

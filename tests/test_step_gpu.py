@@ -348,9 +348,12 @@ def test_mixed_class_batch_against_oracle(gpu_device):
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_graph_replay_matches_eager_steps(gpu_device, precision):
-    """hipGraph replay (kd6d/graph.py: 2 captured graphs + device-resident lr/bias corrections) trains
-    exactly like the eager launch sequence: same losses and same parameters after 4 steps with a
-    moving OneCycle learning rate and changing batches.  (The capture warm-up must not train.)"""
+    """hipGraph replay (kd6d/graph.py: the captured step + device-resident lr/bias corrections) trains
+    like the eager launch sequence: same losses and same parameters after 4 steps with a moving OneCycle
+    learning rate and changing batches, up to the order in which sums are formed -- the replayed step forks its
+    weight gradients onto side streams with a share of the CUs each and sizes the grouped head launch for its launch
+    mode, the eager one runs them in line on the whole device, so their split-K partial sums may differ in number and
+    order.  (The sources hold no float atomics, tests/test_abi.py.  The capture warm-up must not train.)"""
     from kd6d.graph import GraphedKDStep
     from kd6d.kd_losses import PackedTargets
     from kd6d.libs.poses import ImageList
@@ -401,10 +404,11 @@ def test_graph_replay_matches_eager_steps(gpu_device, precision):
     assert n_e == n_g == 4
     assert np.isfinite(h_e).all() and h_e[:, 2].max() > 0, "the KD term must be active in this test"
     # step 1 sees identical weights in both runs (the capture warm-up is rolled back): only the order of
-    # the fp32 atomics differs.  Later steps drift apart the way two eager runs do: AdamW's first
-    # updates are +-lr * sign(g), which amplifies that noise on near-zero gradients.
+    # the fp32 partial sums differs (another split of the weight gradients, see above).  Later steps drift apart
+    # the way two differently split runs do: AdamW's first updates are +-lr * sign(g), which amplifies that
+    # difference on near-zero gradients.
     tol = 1e-3 if precision == "fp32" else 2e-2
-    # the global grad norm sums thousands of atomically accumulated terms: fp32 moves ~1e-3 run to run, bf16 ~2e-2
+    # the global grad norm sums thousands of terms accumulated in another order: fp32 moves ~1e-3, bf16 ~2e-2
     gtol = np.array([tol, tol, tol, 5e-3 if precision == "fp32" else 6e-2])
     assert (np.abs(h_g[0] - h_e[0]) <= np.abs(h_e[0]) * gtol).all(), (h_g[0], h_e[0])
     np.testing.assert_allclose(h_g[1:, :3], h_e[1:, :3], rtol=0.1)
