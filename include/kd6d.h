@@ -521,6 +521,48 @@ int kd6d_sinkhorn_div_fwd_bwd(const float* xs, const float* alpha, const int32_t
                               float* grad_xs, float* grad_alpha, void* stream);
 int kd6d_sinkhorn_max_points(void);
 
+/* ---- kernel distances (csrc/kernel_loss.hip; added under ABI 11, new symbols only): geomloss.SamplesLoss("gaussian" |
+ * "laplacian" | "energy", blur) -- the kernel (MMD) losses of the reference's --gtype -- and their autograd, restated
+ * from geomloss 0.2.4 kernel_samples.py (tensorized path; geomloss is absent from the reference tree: parity unpinned
+ * at that boundary).  For x (N,D) with weights a and y (M,D) with weights b, the weights used as given (not
+ * normalised):
+ *   L = 1/2 sum_ij a_i a_j k(x_i,x_j) + 1/2 sum_ij b_i b_j k(y_i,y_j) - sum_ij a_i b_j k(x_i,y_j),
+ *   r2(u,v) = sum_d (u_d - v_d)^2 from direct differences,
+ *   gaussian k = exp(-r2 / (2 blur^2)); laplacian k = exp(-sqrt(max(r2 / blur^2, 1e-8))); energy k = -sqrt(max(r2, 1e-8)),
+ *   dL/da_i = sum_j a_j k(x_i,x_j) - sum_j b_j k(x_i,y_j),
+ *   dL/dx_i = a_i [ sum_j a_j grad1 k(x_i,x_j) - sum_j b_j grad1 k(x_i,y_j) ],
+ * with grad1 k = 0 where the clamp is active (torch's clamp_min rule: the gradient passes at equality, is zero below):
+ * coincident points, the diagonal included, contribute k = -1e-4 (energy) or exp(-1e-4) (laplacian) and no gradient.
+ * Weights enter as values, never as logarithms: a weight of 0 is an ordinary value.  blur is ignored by the energy
+ * distance and must be > 0 for the other two.
+ * kd6d_kernel_div_fwd_bwd: the KD step's launch, with the layouts and the contract of kd6d_sinkhorn_div_fwd_bwd (D = 2,
+ *   eight keypoint problems per segment pair): problem b uses student points xs[(s_start[b]+i)*8+k][2] (i < s_cnt[b]) with
+ *   weights alpha[(..)*8+k] and teacher points / weights likewise.  loss_kp (optional, n_images*8) = the eight L_k,
+ *   loss_img[b] = their fp32 sum in keypoint order, grad_xs / grad_alpha = d loss_img / d xs, alpha.  valid_img[b] = 1;
+ *   0 and loss 0 when a set is empty; -1 and loss 0 when a set holds more than kd6d_kernel_div_max_points() (= 128 =
+ *   kd6d_sinkhorn_max_points()) points.  Gradient rows of problems with valid_img[b] <= 0, and rows in no segment,
+ *   are NOT written.  Segments may lie in any order, with gaps; a problem's results depend on its own rows only (two
+ *   launches, or the problem launched alone, agree bitwise), and permuting the keypoint axis of all inputs permutes the
+ *   results.  n_images = 0 launches nothing.  One workgroup per problem, one wave per keypoint, one pass over the
+ *   pairs; every sum in a fixed order.
+ * kd6d_kernel_dense_fwd_bwd: ONE problem, D in {2,4,8,16}, N, M >= 1 of any size (the counterpart of
+ *   kd6d_sinkhorn_dense_fwd_bwd); the pair matrices are never materialised (one row per thread, column tiles staged in
+ *   LDS, columns in ascending order).  workspace: kd6d_kernel_dense_workspace_floats(N, M, D) floats, any contents
+ *   (one partial of L per workgroup, added in index order by a last pass).  Outputs: loss (1), grad_x (N,D),
+ *   grad_alpha (N).  Two launches agree bitwise.  fp32 vector arithmetic only. */
+#define KD6D_KERNEL_GAUSSIAN 0
+#define KD6D_KERNEL_LAPLACIAN 1
+#define KD6D_KERNEL_ENERGY 2
+int kd6d_kernel_div_fwd_bwd(int kind, const float* xs, const float* alpha, const int32_t* s_start,
+                            const int32_t* s_cnt, const float* yt, const float* beta, const int32_t* t_start,
+                            const int32_t* t_cnt, int n_images, float blur, float* loss_img, int32_t* valid_img,
+                            float* loss_kp, float* grad_xs, float* grad_alpha, void* stream);
+int kd6d_kernel_div_max_points(void);
+int64_t kd6d_kernel_dense_workspace_floats(int N, int M, int D);
+int kd6d_kernel_dense_fwd_bwd(int kind, const float* x, const float* alpha, const float* y, const float* beta, int N,
+                              int M, int D, float blur, float* workspace, int64_t workspace_floats, float* loss,
+                              float* grad_x, float* grad_alpha, void* stream);
+
 /* ---- loss-side kernels (cls logits (rows,16) fp32 [15 classes + pad], reg logits (rows,240)) --
  * kd6d_teacher_select  <- postprocess/postprocess_kd.py:22-203 (PnP gate treated as true):
  *   slot layout: image b owns slots [b*cap, b*cap + t_cnt[b]); t_kp (slots,8,2) full-frame px,

@@ -34,6 +34,8 @@ EXTRA_FLAGS = {"sinkhorn_dense.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # for the last 16 lanes of a wave (tests/flake_hunt.py); with scalar fp32 instructions it does not happen
                "losses.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "sinkhorn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # kernel_loss.hip: takes sinkhorn.hip's place in the step under --kd_kernel_losses, same switch
+               "kernel_loss.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # augment.hip runs in the loader, beside the other network's convolutions in pipelined mode: same switch
                "augment.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # pnp.hip: the teacher PnP gate runs on the teacher's stream, beside the student's convolutions

@@ -20,6 +20,7 @@ ACC_ACT, ACC_GRAD = 32, 52           # KD6D_ACC_ACT / KD6D_ACC_GRAD: fixed-point
 NORM_GROUP, NORM_BATCH = 1, 2
 BN_FUSED_REPLICAS = 8
 NORM_MAX_CTILES = 8
+KERNEL_KINDS = {"gaussian": 0, "laplacian": 1, "energy": 2}      # KD6D_KERNEL_GAUSSIAN / _LAPLACIAN / _ENERGY
 
 
 class Seg(ctypes.Structure):
@@ -154,6 +155,10 @@ SIGNATURES = {
     "kd6d_image_to_nhwc": [_I, _P, _P, _I, _I, _I, _I, _I, _P],
     "kd6d_sinkhorn_div_fwd_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P],
     "kd6d_sinkhorn_max_points": [],
+    "kd6d_kernel_div_fwd_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P],
+    "kd6d_kernel_div_max_points": [],
+    "kd6d_kernel_dense_workspace_floats": [_I, _I, _I],
+    "kd6d_kernel_dense_fwd_bwd": [_I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _I64, _P, _P, _P, _P],
     "kd6d_sinkhorn_dense_workspace_floats": [_I, _I, _I],
     "kd6d_sinkhorn_dense_diameter": [_P, _P, _I, _I, _I, _P, _P, _P],
     "kd6d_sinkhorn_dense_fwd_bwd": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _D, _P, _I64, _P, _P, _P, _P],

@@ -2,7 +2,7 @@
 
 Every reference flag keeps its name, type and default.  Additive flags of this build:
 --precision {bf16,fp32}, --synthetic, --augment, --skip_teacher_eval, --batch_size (per-step GLOBAL batch,
-overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object,
+overrides SOLVER.IMS_PER_BATCH), --image_size, --mixed_classes, --teacher_pnp_gate, --pnp_solver, --eval_scorer, --kd_per_object, --kd_kernel_losses,
 --synthetic_instances, --frame_cache, --frame_cache_gb, --aug_pose_remap, --aug_chain, --aug_background_gb, --bop_metrics, --bop_vsd, --frame_source and
 the --render_* flags; yaml files may name a `_BASE_` file.
 """
@@ -48,7 +48,10 @@ def get_argparser():
                    choices=["l1", "l2", "sinkhorn", "gaussian", "laplacian", "energy"])
     p.add_argument("--glevel", type=str, default="point", help="level of kd loss", choices=["point"])
     p.add_argument("--p", type=float, default=2.0, help="p of loss_kd_loss")
-    p.add_argument("--blur", type=float, default=0.001, help="blur of loss_kd_loss")
+    p.add_argument("--blur", type=float, default=0.001,
+                   help="blur of loss_kd_loss.  For --gtype gaussian / laplacian it is the kernel's width: the reference's "
+                        "default of 0.001 on frame-normalised coordinates makes such a kernel nearly diagonal (points "
+                        "further apart than a few thousandths of the frame do not see each other)")
     p.add_argument("--gnD", type=int, default=2, help="dimensions of loss_kd_loss")
     p.add_argument("--weightedOT", type=str2bool, nargs="?", const=True, default=True, help="weighted OT of loss_kd_loss")
     p.add_argument("--wot_detach", type=str2bool, nargs="?", const=True, default=False, help="weighted ot with detached cls")
@@ -110,6 +113,11 @@ def get_argparser():
                    help="distil per object: one OT problem per (image, ground-truth instance) -- the instance's positives "
                         "against the teacher's cells of its class -- instead of one per image (the reference's rule, "
                         "correct for one object per image only).  Not with --teacher_pnp_gate")
+    p.add_argument("--kd_kernel_losses", action="store_true",
+                   help="accept --gtype gaussian / laplacian / energy: geomloss' kernel distances (MMD) between the "
+                        "student's and the teacher's weighted keypoint votes, in one pass over the pairs "
+                        "(csrc/kernel_loss.hip) in the Sinkhorn launch's place; --p, --scaling and --reach do not enter "
+                        "them.  Without this flag only --gtype sinkhorn is accepted")
     p.add_argument("--synthetic_instances", type=int, default=1, choices=[1, 2, 3, 4],
                    help="--synthetic: objects of distinct classes per image (masks in vertical strips)")
     add_frame_cache_flags(p)
@@ -306,6 +314,8 @@ def build_cfgs(args):
     if getattr(args, "kd_per_object", False):      # both modules read it: the teacher selects, the student solves per object
         cfg["KD"]["PER_OBJECT"] = True
         cfg_t["KD"]["PER_OBJECT"] = True
+    if getattr(args, "kd_kernel_losses", False):   # the student's loss alone reads it
+        cfg["KD"]["KERNEL_LOSSES"] = True
     return cfg, cfg_t
 
 

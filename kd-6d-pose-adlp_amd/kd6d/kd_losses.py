@@ -21,6 +21,26 @@ PER_OBJECT_GATE_ERROR = ("--kd_per_object cannot be combined with --teacher_pnp_
                          "from the image's cells, a per-object gate is not implemented")
 
 
+def check_gtype(gtype, kernel_losses, blur):
+    """The one rule for --gtype / SamplesLoss(loss): -> None for 'sinkhorn', the KD6D_KERNEL_* code for a kernel
+    distance when kernel_losses (--kd_kernel_losses, SamplesLoss(kernel_losses=True)) opts in; everything else is refused."""
+    if gtype == "sinkhorn":
+        return None
+    if gtype in ("l1", "l2"):
+        raise NotImplementedError("--gtype %s: geomloss has no such loss (geomloss.SamplesLoss knows sinkhorn, hausdorff, "
+                                  "energy, gaussian and laplacian; the reference itself fails on %r)" % (gtype, gtype))
+    if gtype not in _lib.KERNEL_KINDS:
+        raise NotImplementedError("only --gtype sinkhorn, gaussian, laplacian and energy are implemented on the HIP path "
+                                  "(got %r)" % (gtype,))
+    if not kernel_losses:
+        raise NotImplementedError("only --gtype sinkhorn is implemented on the HIP path by default (got %r): the kernel "
+                                  "distances gaussian / laplacian / energy are opt-in, pass --kd_kernel_losses "
+                                  "(cfg['KD']['KERNEL_LOSSES'], SamplesLoss(kernel_losses=True))" % (gtype,))
+    if gtype != "energy" and not blur > 0:
+        raise ValueError("--gtype %s needs --blur > 0 (got %r)" % (gtype, blur))
+    return _lib.KERNEL_KINDS[gtype]
+
+
 def positives_bound(positive_num, n_levels=_lib.MAX_SEG, instances=MAX_GT):
     """Most positive cells kd6d_ssc_assign can pick in one image: per instance the per-level shares of positive_num,
     each rounded half up, i.e. at most floor(positive_num + 0.5 * levels) (include/kd6d.h, kd6d_ssc_assign)."""
@@ -349,8 +369,10 @@ class KDLoss:
         self.gamma, self.alpha = float(gamma), float(alpha)
         self.positive_num, self.positive_lambda = float(positive_num), float(positive_lambda)
         kd_cfg = kd_cfg or {}
-        if kd_cfg.get("GTYPE", "sinkhorn") != "sinkhorn":
-            raise NotImplementedError("only --gtype sinkhorn is implemented on the HIP path (got %r)" % kd_cfg.get("GTYPE"))
+        # KERNEL_LOSSES (--kd_kernel_losses): GTYPE may also name one of geomloss' kernel distances; the KD term is
+        # then kd6d_kernel_div_fwd_bwd in the Sinkhorn launch's place (self.kernel = its KD6D_KERNEL_* code)
+        self.kernel = check_gtype(kd_cfg.get("GTYPE", "sinkhorn"), bool(kd_cfg.get("KERNEL_LOSSES", False)),
+                                  float(kd_cfg.get("GBLUR", 0.001)))
         if kd_cfg.get("GLEVEL", "point") != "point" or int(kd_cfg.get("GnD", 2)) != 2:
             raise NotImplementedError("only --glevel point / --gnD 2 are implemented")
         self.p = float(kd_cfg.get("GP", 2.0))
@@ -461,6 +483,21 @@ class KDLoss:
                                   P(pos_row), P(pos_gt), ops._stream()), "kd6d_ssc_assign")
         return dict(rows=rows, levels=tuple(levels), batch=batch, labels=labels, wf=wf, wi=wi, keys=keys)
 
+    def _divergence(self, xs, alpha, start, cnt, teacher, n, loss, valid, g_xs, g_alpha, st):
+        """The KD term's one launch over n problems (student segments start / cnt, the teacher's own): the Sinkhorn
+        divergence, or the kernel distance self.kernel names.  Same buffers, same contract for both."""
+        P = ops._ptr
+        if self.kernel is None:
+            check(lib.kd6d_sinkhorn_div_fwd_bwd(P(xs), P(alpha), P(start), P(cnt), P(teacher.t_kp_norm),
+                                                P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), n, self.p,
+                                                self.blur, self.scaling, self.reach, P(loss), P(valid), None,
+                                                P(g_xs), P(g_alpha), st), "kd6d_sinkhorn_div_fwd_bwd")
+        else:       # p, scaling and reach do not enter a kernel distance (geomloss ignores them alike)
+            check(lib.kd6d_kernel_div_fwd_bwd(self.kernel, P(xs), P(alpha), P(start), P(cnt), P(teacher.t_kp_norm),
+                                              P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), n, self.blur,
+                                              P(loss), P(valid), None, P(g_xs), P(g_alpha), st),
+                  "kd6d_kernel_div_fwd_bwd")
+
     def forward(self, cls_s, reg_s, levels, batch, tgt, teacher, keys=None, seg_scale=None, pre=None):
         dev = cls_s.device
         rows = cls_s.shape[0]
@@ -514,20 +551,14 @@ class KDLoss:
             o_start, o_cnt, o_valid, dest = (part(wi, seg_i, k) for k in ("obj_start", "obj_cnt", "valid_obj", "dest"))
             check(lib.kd6d_kd_group_objects(P(pos_cnt), P(pos_gt), P(xs), P(alpha), batch, cap, P(o_start), P(o_cnt),
                                             P(dest), P(xs_o), P(al_o), st), "kd6d_kd_group_objects")
-            check(lib.kd6d_sinkhorn_div_fwd_bwd(P(xs_o), P(al_o), P(o_start), P(o_cnt), P(teacher.t_kp_norm),
-                                                P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), nobj, self.p,
-                                                self.blur, self.scaling, self.reach, P(loss_obj), P(o_valid), None,
-                                                P(g_xs_o), P(g_al_o), st), "kd6d_sinkhorn_div_fwd_bwd")
+            self._divergence(xs_o, al_o, o_start, o_cnt, teacher, nobj, loss_obj, o_valid, g_xs_o, g_al_o, st)
             check(lib.kd6d_kd_mean(P(loss_obj), P(o_valid), nobj, P(losses[2:3]), P(n_valid), st), "kd6d_kd_mean")
             check(lib.kd6d_kd_scatter_objects(P(pos_cnt), P(pos_gt), P(dest), P(o_valid), P(g_xs_o), P(g_al_o), batch,
                                               cap, P(g_xs), P(g_alpha), P(valid), st), "kd6d_kd_scatter_objects")
             self.obj = dict(start=o_start, cnt=o_cnt, valid=o_valid, dest=dest, loss=loss_obj, xs=xs_o, alpha=al_o,
                             g_xs=g_xs_o, g_alpha=g_al_o)
         elif teacher is not None:
-            check(lib.kd6d_sinkhorn_div_fwd_bwd(P(xs), P(alpha), P(s_start), P(pos_cnt), P(teacher.t_kp_norm),
-                                                P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), batch, self.p,
-                                                self.blur, self.scaling, self.reach, P(loss_img), P(valid), None,
-                                                P(g_xs), P(g_alpha), st), "kd6d_sinkhorn_div_fwd_bwd")
+            self._divergence(xs, alpha, s_start, pos_cnt, teacher, batch, loss_img, valid, g_xs, g_alpha, st)
             check(lib.kd6d_kd_mean(P(loss_img), P(valid), batch, P(losses[2:3]), P(n_valid), st), "kd6d_kd_mean")
         self.ctx = dict(lv=lv, cls=cls_s, reg=reg_s, labels=labels, pos_cnt=pos_cnt, pos_row=pos_row, pos_gt=pos_gt,
                         tgt=tgt, g_reg=g_reg, g_xs=g_xs, g_alpha=g_alpha, n_valid=n_valid, valid=valid,

@@ -9,7 +9,7 @@ import os
 import torch
 
 from .. import ops
-from ..kd_losses import KDLoss, PackedTargets, TeacherKnowledge
+from ..kd_losses import KDLoss, PackedTargets, TeacherKnowledge, check_gtype
 
 _DENSE_DIMS = (2, 4, 8, 16)
 
@@ -68,17 +68,70 @@ class _SinkhornBatchFn(torch.autograd.Function):
         return (g[:, None] * ga).to(adt), (g[:, None, None] * gx).to(xdt), None, None, None, None, None, None
 
 
+class _KernelBatchFn(torch.autograd.Function):
+    """(alpha (B,N), x (B,N,D), beta (B,M), y (B,M,D)) -> (B,) kernel distances (kind = a KD6D_KERNEL_* code).
+    Gradients reach alpha and x."""
+
+    @staticmethod
+    def forward(ctx, alpha, x, beta, y, kind, blur):
+        B, N, D = x.shape
+        M = y.shape[1]
+        dev = x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        xd, yd = x.detach().to(torch.float32), y.detach().to(torch.float32)
+        ad, bd = alpha.detach().to(torch.float32), beta.detach().to(torch.float32)
+        cap = ops.lib.kd6d_kernel_div_max_points()
+        if D == 2 and B <= 8 and N <= cap and M <= cap:
+            # one workgroup, one wave per problem; a batch shorter than 8 is filled with copies of problem 0, whose
+            # results are dropped (the problems are independent: nothing like the Sinkhorn's joint diameter here)
+            idx = torch.cat([torch.arange(B, device=dev), torch.zeros(8 - B, dtype=torch.long, device=dev)])
+            xs = xd[idx].permute(1, 0, 2).contiguous()            # (N,8,2)
+            yt = yd[idx].permute(1, 0, 2).contiguous()
+            al = ad[idx].t().contiguous()                         # (N,8)
+            be = bd[idx].t().contiguous()
+            i32 = dict(dtype=torch.int32, device=dev)
+            zero = torch.zeros(1, **i32)
+            loss_kp = torch.empty(1, 8, **f32)
+            _, valid, gx, ga = ops.kernel_div(kind, xs, al, zero, torch.full((1,), N, **i32), yt, be, zero,
+                                              torch.full((1,), M, **i32), 1, blur, loss_kp=loss_kp)
+            out = loss_kp[0, :B].clone()
+            gx, ga = gx.permute(1, 0, 2)[:B].contiguous(), ga.t()[:B].contiguous()
+        elif D in _DENSE_DIMS:
+            out = torch.empty(B, **f32)
+            gx, ga = torch.empty(B, N, D, **f32), torch.empty(B, N, **f32)
+            for b in range(B):
+                l, g1, g2 = ops.kernel_dense(kind, xd[b].contiguous(), ad[b].contiguous(), yd[b].contiguous(),
+                                             bd[b].contiguous(), blur)
+                out[b:b + 1].copy_(l)
+                gx[b].copy_(g1)
+                ga[b].copy_(g2)
+        else:
+            raise NotImplementedError("SamplesLoss on the HIP path: D=2 with <= %d points per set, or D in %s for "
+                                      "larger sets (got D=%d)" % (cap, _DENSE_DIMS, D))
+        ctx.save_for_backward(gx, ga)
+        ctx.dtypes = (alpha.dtype, x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, ga = ctx.saved_tensors
+        adt, xdt = ctx.dtypes
+        return (g[:, None] * ga).to(adt), (g[:, None, None] * gx).to(xdt), None, None, None, None
+
+
 class SamplesLoss:
     """geomloss.SamplesLoss(loss, p, blur, scaling, reach) as the reference builds it (losses/kd_loss.py:26-30):
     `L(alpha, x, beta, y) -> (B,)` for alpha (B,N), x (B,N,D), beta (B,M), y (B,M,D); `L(x, y)` uses uniform weights
     1/N, 1/M.  Debiased (unbalanced when reach is set) Sinkhorn divergence, cost |x-y|^2/2, epsilon-scaling from
     diameter^2 to blur^2; gradients flow into alpha and x (the student side of the KD loss), y and beta are
-    constants (the reference feeds the teacher's no-grad outputs there)."""
+    constants (the reference feeds the teacher's no-grad outputs there).
+    kernel_losses=True (additive keyword of this build) also accepts loss = 'gaussian' | 'laplacian' | 'energy':
+    geomloss' kernel distances (csrc/kernel_loss.hip, the weights used as given); p, scaling and reach are accepted
+    and ignored for them, as geomloss does."""
 
-    def __init__(self, loss="sinkhorn", p=2, blur=0.05, scaling=0.5, reach=None, **unsupported):
-        if loss != "sinkhorn":
-            raise NotImplementedError("only loss='sinkhorn' is implemented on the HIP path (got %r)" % (loss,))
-        if float(p) != 2.0:
+    def __init__(self, loss="sinkhorn", p=2, blur=0.05, scaling=0.5, reach=None, kernel_losses=False, **unsupported):
+        self.kernel = check_gtype(loss, bool(kernel_losses), float(blur))
+        if self.kernel is None and float(p) != 2.0:
             raise NotImplementedError("only p=2 is implemented on the HIP path (got %r)" % (p,))
         if unsupported:
             raise NotImplementedError("SamplesLoss options not implemented on the HIP path: %s" % sorted(unsupported))
@@ -100,7 +153,10 @@ class SamplesLoss:
             raise NotImplementedError("gradients w.r.t. the second measure (beta, y) are not computed on the HIP path")
         if not x.is_cuda:
             raise RuntimeError("kd6d SamplesLoss runs on the GPU only (no CPU fallback)")
-        out = _SinkhornBatchFn.apply(alpha, x, beta, y, self.p, self.blur, self.scaling, self.reach)
+        if self.kernel is not None:
+            out = _KernelBatchFn.apply(alpha, x, beta, y, self.kernel, self.blur)
+        else:
+            out = _SinkhornBatchFn.apply(alpha, x, beta, y, self.p, self.blur, self.scaling, self.reach)
         return out[0] if squeeze else out
 
 
@@ -174,7 +230,8 @@ class KDPoseLoss:
         self.impl.anchor_sizes, self.impl.anchor_strides = self.anchor_sizes, self.anchor_strides
         if cfg_kd is not None:
             self.kd_loss = SamplesLoss(cfg_kd["GTYPE"], p=cfg_kd["GP"], blur=cfg_kd["GBLUR"],
-                                       scaling=cfg_kd["SCALING"], reach=cfg_kd["REACH"])
+                                       scaling=cfg_kd["SCALING"], reach=cfg_kd["REACH"],
+                                       kernel_losses=bool(cfg_kd.get("KERNEL_LOSSES")))
             self.weighted_ot = cfg_kd["WEIGHTED_OT"]
             self.wot_detach = cfg_kd["DETACH"]
             if "vis_dir" in cfg_kd:

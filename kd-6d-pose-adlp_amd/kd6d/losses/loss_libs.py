@@ -6,7 +6,7 @@ pos_per_img / pos_per_img_t the cells per image.  Returns one scalar per image t
 the sum over the 8 keypoints of kd_loss(alpha, x, beta, y).
 
 With kd6d's SamplesLoss (weighted, level 'point', dim 2, sets within kd6d_sinkhorn_max_points) all images go out as
-ONE kd6d_sinkhorn_div_fwd_bwd launch; any other callable is applied image by image exactly as the reference does.
+ONE kd6d_sinkhorn_div_fwd_bwd launch (kd6d_kernel_div_fwd_bwd for a kernel distance); any other callable is applied image by image exactly as the reference does.
 """
 import torch
 
@@ -21,9 +21,12 @@ class _PackedSinkhornFn(torch.autograd.Function):
         i32 = dict(dtype=torch.int32, device=dev)
         sc, tc = torch.tensor(s_cnt, dtype=torch.int32), torch.tensor(t_cnt, dtype=torch.int32)
         s_start, t_start = (torch.cumsum(sc, 0) - sc).to(**i32), (torch.cumsum(tc, 0) - tc).to(**i32)
-        loss, valid, gx, ga = ops.sinkhorn_div(xs.detach().contiguous(), alpha.detach().contiguous(), s_start, sc.to(**i32),
-                                               yt.detach().contiguous(), beta.detach().contiguous(), t_start, tc.to(**i32),
-                                               len(s_cnt), kd.p, kd.blur, kd.scaling, kd.reach)
+        sets = (xs.detach().contiguous(), alpha.detach().contiguous(), s_start, sc.to(**i32),
+                yt.detach().contiguous(), beta.detach().contiguous(), t_start, tc.to(**i32), len(s_cnt))
+        if kd.kernel is not None:          # SamplesLoss(kernel_losses=True): a kernel distance, same layouts
+            loss, valid, gx, ga = ops.kernel_div(kd.kernel, *sets, kd.blur)
+        else:
+            loss, valid, gx, ga = ops.sinkhorn_div(*sets, kd.p, kd.blur, kd.scaling, kd.reach)
         img_of = torch.repeat_interleave(torch.arange(len(s_cnt)), sc.long()).to(dev)
         ctx.save_for_backward(gx, ga, img_of)
         return loss

@@ -669,6 +669,51 @@ def sinkhorn_div(xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, 
     return loss, valid, gx, ga
 
 
+def kernel_kind(kind):
+    """'gaussian' | 'laplacian' | 'energy' (or the KD6D_KERNEL_* code itself) -> the code."""
+    from ._lib import KERNEL_KINDS
+    if isinstance(kind, str):
+        if kind not in KERNEL_KINDS:
+            raise ValueError("kernel loss %r: expected one of %s" % (kind, sorted(KERNEL_KINDS)))
+        return KERNEL_KINDS[kind]
+    return int(kind)
+
+
+def kernel_div(kind, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, blur, loss_kp=None):
+    """Kernel distance (gaussian / laplacian / energy MMD, csrc/kernel_loss.hip) per problem, with the layouts of
+    sinkhorn_div: xs (P,8,2), alpha (P,8), yt (M,8,2), beta (M,8); problem b owns student rows
+    [s_start[b], s_start[b]+s_cnt[b]) and teacher rows likewise (int32 device arrays).
+    Returns loss_img (B), valid_img (B) int32, grad_xs (P,8,2), grad_alpha (P,8); loss_kp: optional (B,8) fp32
+    output of the eight per-keypoint distances."""
+    dev = xs.device
+    loss = torch.empty(n_images, dtype=torch.float32, device=dev)
+    valid = torch.empty(n_images, dtype=torch.int32, device=dev)
+    gx = torch.zeros_like(xs)
+    ga = torch.zeros_like(alpha)
+    check(lib.kd6d_kernel_div_fwd_bwd(kernel_kind(kind), _ptr(xs), _ptr(alpha), _ptr(s_start), _ptr(s_cnt), _ptr(yt),
+                                      _ptr(beta), _ptr(t_start), _ptr(t_cnt), n_images, blur, _ptr(loss), _ptr(valid),
+                                      _ptr(loss_kp), _ptr(gx), _ptr(ga), _stream()), "kd6d_kernel_div_fwd_bwd")
+    return loss, valid, gx, ga
+
+
+def kernel_dense(kind, x, alpha, y, beta, blur=0.05):
+    """Kernel distance between two weighted point sets of any size: x (N,D), alpha (N), y (M,D), beta (M), D in
+    {2,4,8,16} (kd6d_kernel_dense_fwd_bwd).  Returns loss (1,), dL/dx (N,D), dL/dalpha (N)."""
+    N, D = x.shape
+    M = y.shape[0]
+    dev = x.device
+    assert x.dtype == torch.float32 and y.shape == (M, D) and alpha.shape == (N,) and beta.shape == (M,)
+    nws = int(lib.kd6d_kernel_dense_workspace_floats(N, M, D))
+    ws = torch.empty(max(nws, 1), dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    gx = torch.empty_like(x)
+    ga = torch.empty_like(alpha)
+    check(lib.kd6d_kernel_dense_fwd_bwd(kernel_kind(kind), _ptr(x), _ptr(alpha), _ptr(y), _ptr(beta), N, M, D, blur,
+                                        _ptr(ws), nws, _ptr(loss), _ptr(gx), _ptr(ga), _stream()),
+          "kd6d_kernel_dense_fwd_bwd")
+    return loss, gx, ga
+
+
 def pnp_workspace(n_problems, iters, device):
     """Scratch of kd6d_pnp_ransac / kd6d_teacher_pnp_gate (any contents): keep one per shape across calls."""
     return torch.empty(max(int(lib.kd6d_pnp_workspace_floats(n_problems, iters)), 1), dtype=torch.float32, device=device)
