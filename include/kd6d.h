@@ -500,12 +500,15 @@ int kd6d_image_to_nhwc(int dtype, const float* img_nchw, void* out, int B, int C
  * reach) as called from losses/loss_libs.py:22-51 (one call per image, batch dim = 8 keypoints)
  * and its autograd.  Image b uses student points xs[(s_start[b]+i)*8+k][2] (i < s_cnt[b]) with
  * weights alpha[(..)*8+k] and teacher points/weights likewise; reach <= 0 means balanced.
- * Outputs: loss_img[b] = sum_k S_k (0 when a set is empty: valid_img[b] = 0; -1 = set larger than
- * kd6d_sinkhorn_max_points()), loss_kp (optional, n_images*8) = the eight S_k themselves (what SamplesLoss returns
+ * The small-set launch contract (csrc/pointset_small.h; kd6d_kernel_div_fwd_bwd below keeps the same one): one workgroup
+ *   per problem, one wave per keypoint.
+ * Outputs: loss_img[b] = sum_k S_k, valid_img[b] = 1 (0 when a set is empty; -1 = set larger than
+ * kd6d_sinkhorn_max_points() = 128), loss_kp (optional, n_images*8) = the eight S_k themselves (what SamplesLoss returns
  * for a batch of 8 problems), grad_xs / grad_alpha = d loss_img / d xs, alpha.
  * What is written: grad_xs / grad_alpha rows of problems with valid_img[b] <= 0, and rows that lie in no segment,
- *   are NOT written (callers that scatter or sum whole arrays zero them first, as ops.sinkhorn_div does); loss_img[b]
- *   and the eight loss_kp of such problems are 0.  loss_img[b] is the fp32 sum of the eight loss_kp in keypoint order.
+ *   are NOT written (callers that scatter or sum whole arrays zero them first, as ops.sinkhorn_div does unless it is
+ *   handed out= buffers); loss_img[b] and the eight loss_kp of such problems are 0.  loss_img[b] is the fp32 sum of the
+ *   eight loss_kp in keypoint order.
  *   Segments may lie in any order, with gaps; a problem's results depend on its own rows only (two launches, or
  *   the problem launched alone, agree bitwise), and permuting the keypoint axis of all inputs permutes the results.
  * Small sets: when both sets hold <= 16 points the four softmins of an update run side by side on the four 16-lane
@@ -535,16 +538,11 @@ int kd6d_sinkhorn_max_points(void);
  * coincident points, the diagonal included, contribute k = -1e-4 (energy) or exp(-1e-4) (laplacian) and no gradient.
  * Weights enter as values, never as logarithms: a weight of 0 is an ordinary value.  blur is ignored by the energy
  * distance and must be > 0 for the other two.
- * kd6d_kernel_div_fwd_bwd: the KD step's launch, with the layouts and the contract of kd6d_sinkhorn_div_fwd_bwd (D = 2,
- *   eight keypoint problems per segment pair): problem b uses student points xs[(s_start[b]+i)*8+k][2] (i < s_cnt[b]) with
- *   weights alpha[(..)*8+k] and teacher points / weights likewise.  loss_kp (optional, n_images*8) = the eight L_k,
- *   loss_img[b] = their fp32 sum in keypoint order, grad_xs / grad_alpha = d loss_img / d xs, alpha.  valid_img[b] = 1;
- *   0 and loss 0 when a set is empty; -1 and loss 0 when a set holds more than kd6d_kernel_div_max_points() (= 128 =
- *   kd6d_sinkhorn_max_points()) points.  Gradient rows of problems with valid_img[b] <= 0, and rows in no segment,
- *   are NOT written.  Segments may lie in any order, with gaps; a problem's results depend on its own rows only (two
- *   launches, or the problem launched alone, agree bitwise), and permuting the keypoint axis of all inputs permutes the
- *   results.  n_images = 0 launches nothing.  One workgroup per problem, one wave per keypoint, one pass over the
- *   pairs; every sum in a fixed order.
+ * kd6d_kernel_div_fwd_bwd: the KD step's launch (D = 2, eight keypoint problems per segment pair), under the small-set
+ *   launch contract stated at kd6d_sinkhorn_div_fwd_bwd above -- layouts, valid_img = 1 / 0 / -1 with
+ *   kd6d_kernel_div_max_points() = kd6d_sinkhorn_max_points() = 128, what is and is not written, loss_img as the ordered
+ *   fp32 sum of loss_kp, independence of the problems -- with L_k in the place of S_k.  n_images = 0 launches nothing.
+ *   One pass over the pairs; every sum in a fixed order.
  * kd6d_kernel_dense_fwd_bwd: ONE problem, D in {2,4,8,16}, N, M >= 1 of any size (the counterpart of
  *   kd6d_sinkhorn_dense_fwd_bwd); the pair matrices are never materialised (one row per thread, column tiles staged in
  *   LDS, columns in ascending order).  workspace: kd6d_kernel_dense_workspace_floats(N, M, D) floats, any contents

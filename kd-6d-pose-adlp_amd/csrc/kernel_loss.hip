@@ -17,12 +17,13 @@
 // the layouts and the contract of kd6d_sinkhorn_div_fwd_bwd.  kd6d_kernel_dense_fwd_bwd is the counterpart of
 // kd6d_sinkhorn_dense_fwd_bwd: one problem, D in {2,4,8,16}, one row per thread, column tiles staged in LDS, the
 // pair matrices never materialised.  fp32 VALU only; every sum runs in a fixed order (no atomics).
-#include "kd6d_common.h"
+#include <type_traits>
+
+#include "pointset_small.h"
 
 namespace {
 
-constexpr int kCap = 128;       // max points per set per problem in the small kernel (= kd6d_sinkhorn_max_points())
-constexpr int kWaves = 8;       // keypoints per problem
+using namespace pointset;
 constexpr float kClamp = 1e-8f;
 
 // k and the factor c of its gradient, grad1 k(u,v) = c * (u - v), from r2 = |u - v|^2.
@@ -116,27 +117,24 @@ __global__ __launch_bounds__(64 * kWaves) void kernel_small_kernel(
   __shared__ __attribute__((aligned(16))) WaveLds all[kWaves];
   __shared__ float red[kWaves];
 
-  const int b = blockIdx.x;
+  const Segments sg = small_problem_begin(s_start, s_cnt, t_start, t_cnt, loss_img, valid_img, loss_kp);
+  if (sg.skip) return;
+  const int s0 = sg.s0, N = sg.N(), t0 = sg.t0, M = sg.M();
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
-  const int s0 = s_start[b], N = s_cnt[b];
-  const int t0 = t_start[b], M = t_cnt[b];
-  if (N <= 0 || M <= 0 || N > kCap || M > kCap) {      // empty: skipped like the Sinkhorn launch; too large: -1
-    if (threadIdx.x == 0) { loss_img[b] = 0.f; valid_img[b] = (N <= 0 || M <= 0) ? 0 : -1; }
-    if (loss_kp && threadIdx.x < kWaves) loss_kp[b * kWaves + threadIdx.x] = 0.f;
-    return;
-  }
   WaveLds& L = all[wave];
   const int k = wave;  // keypoint
   for (int i = lane; i < N; i += 64) {
-    L.px[i] = xs[((size_t)(s0 + i) * 8 + k) * 2 + 0];
-    L.py[i] = xs[((size_t)(s0 + i) * 8 + k) * 2 + 1];
-    L.a[i] = alpha[(size_t)(s0 + i) * 8 + k];
+    const size_t at = weight_at(s0 + i, k);
+    L.px[i] = xs[point_at(at) + 0];
+    L.py[i] = xs[point_at(at) + 1];
+    L.a[i] = alpha[at];
   }
   for (int j = lane; j < M; j += 64) {
-    L.qx[j] = yt[((size_t)(t0 + j) * 8 + k) * 2 + 0];
-    L.qy[j] = yt[((size_t)(t0 + j) * 8 + k) * 2 + 1];
-    L.b[j] = beta[(size_t)(t0 + j) * 8 + k];
+    const size_t at = weight_at(t0 + j, k);
+    L.qx[j] = yt[point_at(at) + 0];
+    L.qy[j] = yt[point_at(at) + 1];
+    L.b[j] = beta[at];
   }
   __syncthreads();
 
@@ -147,24 +145,17 @@ __global__ __launch_bounds__(64 * kWaves) void kernel_small_kernel(
     const float sxx = row_sweep<KIND, true>(rx, ry, L.px, L.py, L.a, N, inv_b2, gxx0, gxx1);
     const float sxy = row_sweep<KIND, true>(rx, ry, L.qx, L.qy, L.b, M, inv_b2, gxy0, gxy1);
     part += a * (0.5f * sxx - sxy);
-    gx_out[((size_t)(s0 + i) * 8 + k) * 2 + 0] = a * (gxx0 - gxy0);
-    gx_out[((size_t)(s0 + i) * 8 + k) * 2 + 1] = a * (gxx1 - gxy1);
-    galpha_out[(size_t)(s0 + i) * 8 + k] = sxx - sxy;
+    const size_t at = weight_at(s0 + i, k);
+    gx_out[point_at(at) + 0] = a * (gxx0 - gxy0);
+    gx_out[point_at(at) + 1] = a * (gxx1 - gxy1);
+    galpha_out[at] = sxx - sxy;
   }
   for (int j = lane; j < M; j += 64) {           // third sweep: rows of y over the y columns, value only
     float g0, g1;
     const float syy = row_sweep<KIND, false>(L.qx[j], L.qy[j], L.qx, L.qy, L.b, M, inv_b2, g0, g1);
     part += 0.5f * L.b[j] * syy;
   }
-  part = wave_sum(part);
-  if (lane == 0) { red[wave] = part; if (loss_kp) loss_kp[b * kWaves + wave] = part; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int w = 0; w < kWaves; ++w) tot += red[w];
-    loss_img[b] = tot;
-    valid_img[b] = 1;
-  }
+  small_problem_finish(part, red, loss_img, valid_img, loss_kp);
 }
 
 // ---- dense sets: one problem, D coordinates per point -----------------------------------------------------------
@@ -272,29 +263,17 @@ __global__ void kernel_dense_sum_kernel(const float* __restrict__ partials, int 
   }
 }
 
-template <int KIND>
-void launch_small(hipStream_t st, const float* xs, const float* alpha, const int32_t* s_start, const int32_t* s_cnt,
-                  const float* yt, const float* beta, const int32_t* t_start, const int32_t* t_cnt, int n_images,
-                  float inv_b2, float* loss_img, int32_t* valid_img, float* loss_kp, float* grad_xs, float* grad_alpha) {
-  hipLaunchKernelGGL(kernel_small_kernel<KIND>, dim3(n_images), dim3(64 * kWaves), 0, st, xs, alpha, s_start, s_cnt, yt,
-                     beta, t_start, t_cnt, inv_b2, loss_img, valid_img, loss_kp, grad_xs, grad_alpha);
+// f(std::integral_constant<int, KIND>) for the KD6D_KERNEL_* code `kind`; f(std::integral_constant<int, D>) for D
+template <int V> using Const = std::integral_constant<int, V>;
+template <class F>
+void dispatch_kind(int kind, F f) {
+  if (kind == KD6D_KERNEL_GAUSSIAN) f(Const<KD6D_KERNEL_GAUSSIAN>{});
+  else if (kind == KD6D_KERNEL_LAPLACIAN) f(Const<KD6D_KERNEL_LAPLACIAN>{});
+  else f(Const<KD6D_KERNEL_ENERGY>{});
 }
-
-template <int KIND>
-void launch_dense(hipStream_t st, const float* x, const float* alpha, const float* y, const float* beta, int N, int M,
-                  int D, float inv_b2, float* partials, float* grad_x, float* grad_alpha) {
-  const int nbx = cdiv(N, kRows), nby = cdiv(M, kRows);
-  const dim3 grid(nbx + nby), block(kRows);
-  switch (D) {
-    case 2: hipLaunchKernelGGL((kernel_dense_kernel<KIND, 2>), grid, block, 0, st, x, alpha, y, beta, N, M, nbx, inv_b2,
-                               partials, grad_x, grad_alpha); break;
-    case 4: hipLaunchKernelGGL((kernel_dense_kernel<KIND, 4>), grid, block, 0, st, x, alpha, y, beta, N, M, nbx, inv_b2,
-                               partials, grad_x, grad_alpha); break;
-    case 8: hipLaunchKernelGGL((kernel_dense_kernel<KIND, 8>), grid, block, 0, st, x, alpha, y, beta, N, M, nbx, inv_b2,
-                               partials, grad_x, grad_alpha); break;
-    default: hipLaunchKernelGGL((kernel_dense_kernel<KIND, 16>), grid, block, 0, st, x, alpha, y, beta, N, M, nbx, inv_b2,
-                                partials, grad_x, grad_alpha); break;
-  }
+template <class F>
+void dispatch_dim(int D, F f) {
+  if (D == 2) f(Const<2>{}); else if (D == 4) f(Const<4>{}); else if (D == 8) f(Const<8>{}); else f(Const<16>{});
 }
 
 // 1 / blur^2 in double like the reference's python floats; the energy distance has no blur
@@ -309,9 +288,9 @@ extern "C" int kd6d_kernel_div_fwd_bwd(int kind, const float* xs, const float* a
                                        const int32_t* t_cnt, int n_images, float blur, float* loss_img,
                                        int32_t* valid_img, float* loss_kp, float* grad_xs, float* grad_alpha,
                                        void* stream) {
-  KD6D_CHECK_ARG(xs && alpha && s_start && s_cnt && yt && beta && t_start && t_cnt && loss_img && valid_img && grad_xs &&
-                     grad_alpha,
-                 "kd6d_kernel_div_fwd_bwd: null pointer");
+  if (const int rc = check_small_set_pointers("kd6d_kernel_div_fwd_bwd", xs, alpha, s_start, s_cnt, yt, beta, t_start,
+                                              t_cnt, loss_img, valid_img, grad_xs, grad_alpha))
+    return rc;
   KD6D_CHECK_ARG(kind >= KD6D_KERNEL_GAUSSIAN && kind <= KD6D_KERNEL_ENERGY, "kd6d_kernel_div_fwd_bwd: unknown kind=%d",
                  kind);
   KD6D_CHECK_ARG(kind == KD6D_KERNEL_ENERGY || blur > 0.f, "kd6d_kernel_div_fwd_bwd: blur=%g (need blur > 0)",
@@ -320,15 +299,10 @@ extern "C" int kd6d_kernel_div_fwd_bwd(int kind, const float* xs, const float* a
   if (n_images == 0) return KD6D_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const float inv_b2 = inv_blur2(kind, blur);
-  if (kind == KD6D_KERNEL_GAUSSIAN)
-    launch_small<KD6D_KERNEL_GAUSSIAN>(st, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, inv_b2, loss_img,
-                                       valid_img, loss_kp, grad_xs, grad_alpha);
-  else if (kind == KD6D_KERNEL_LAPLACIAN)
-    launch_small<KD6D_KERNEL_LAPLACIAN>(st, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, inv_b2, loss_img,
-                                        valid_img, loss_kp, grad_xs, grad_alpha);
-  else
-    launch_small<KD6D_KERNEL_ENERGY>(st, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, inv_b2, loss_img,
-                                     valid_img, loss_kp, grad_xs, grad_alpha);
+  dispatch_kind(kind, [&](auto K) {
+    hipLaunchKernelGGL(kernel_small_kernel<decltype(K)::value>, dim3(n_images), dim3(64 * kWaves), 0, st, xs, alpha,
+                       s_start, s_cnt, yt, beta, t_start, t_cnt, inv_b2, loss_img, valid_img, loss_kp, grad_xs, grad_alpha);
+  });
   KD6D_CHECK_LAUNCH("kd6d_kernel_div_fwd_bwd");
   return KD6D_OK;
 }
@@ -357,12 +331,13 @@ extern "C" int kd6d_kernel_dense_fwd_bwd(int kind, const float* x, const float* 
                  (long long)workspace_floats, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const float inv_b2 = inv_blur2(kind, blur);
-  if (kind == KD6D_KERNEL_GAUSSIAN)
-    launch_dense<KD6D_KERNEL_GAUSSIAN>(st, x, alpha, y, beta, N, M, D, inv_b2, workspace, grad_x, grad_alpha);
-  else if (kind == KD6D_KERNEL_LAPLACIAN)
-    launch_dense<KD6D_KERNEL_LAPLACIAN>(st, x, alpha, y, beta, N, M, D, inv_b2, workspace, grad_x, grad_alpha);
-  else
-    launch_dense<KD6D_KERNEL_ENERGY>(st, x, alpha, y, beta, N, M, D, inv_b2, workspace, grad_x, grad_alpha);
+  const int nbx = cdiv(N, kRows), nby = cdiv(M, kRows);
+  dispatch_kind(kind, [&](auto K) {
+    dispatch_dim(D, [&](auto Dc) {
+      hipLaunchKernelGGL((kernel_dense_kernel<decltype(K)::value, decltype(Dc)::value>), dim3(nbx + nby), dim3(kRows), 0,
+                         st, x, alpha, y, beta, N, M, nbx, inv_b2, workspace, grad_x, grad_alpha);
+    });
+  });
   KD6D_CHECK_LAUNCH("kd6d_kernel_dense_fwd_bwd");
   hipLaunchKernelGGL(kernel_dense_sum_kernel, dim3(1), dim3(64), 0, st, workspace, (int)need, loss);
   KD6D_CHECK_LAUNCH("kd6d_kernel_dense_fwd_bwd");

@@ -13,13 +13,13 @@
 // (they share the epsilon schedule: the diameter is taken over all 8*(N+M) points).
 // Lane i owns row i of every softmin; column data and potentials live in the wave's
 // private LDS slice and are read as broadcasts.  ~400 tiny launches + one .item() sync
-// per image in the reference become 1 launch per step.
-#include "kd6d_common.h"
+// per image in the reference become 1 launch per step.  Constants, addressing and the block total are the small-set
+// frame of pointset_small.h; the skip block is this kernel's own copy of small_problem_begin (profiles/pointset_frame.md).
+#include "pointset_small.h"
 
 namespace {
 
-constexpr int kCap = 128;     // max points per set per image in this kernel
-constexpr int kWaves = 8;     // keypoints per image
+using namespace pointset;
 constexpr float kNegLog = -100000.f;
 
 struct WaveLds {
@@ -76,6 +76,38 @@ __device__ __forceinline__ float lse_row(float rx, float ry, const float* cx, co
   return m + logf(s);
 }
 
+struct EpsStep { float lam, feps, inv; };               // damping 1/(1 + eps/rho), eps, 1/eps of one step
+struct Marginals { bool unbalanced; float w_unb, inv_rho, lam; };   // the last step's (rho + eps/2), 1/rho, damping
+
+// Row i of x after the last extrapolation: potentials a_x (x over x) and b_x (x over y) with the softmax-weighted
+// differences gxx, gxy of their softmins, weight a.  Stores d loss / d x_i and d loss / d alpha_i at `at`; returns the
+// row's term of the debiased cost.
+__device__ __forceinline__ float finish_x_row(float a_x, float b_x, float2 gxx, float2 gxy, float a, const Marginals& m,
+                                              float* __restrict__ gx_out, float* __restrict__ galpha_out, size_t at) {
+  float dS_da, gx0, gx1;
+  if (m.unbalanced) {
+    const float ea = expf(-a_x * m.inv_rho), eb = expf(-b_x * m.inv_rho);
+    dS_da = m.w_unb * (ea - eb);
+    const float c = -a * m.w_unb * m.inv_rho * m.lam;
+    gx0 = c * (ea * gxx.x - eb * gxy.x);
+    gx1 = c * (ea * gxx.y - eb * gxy.y);
+  } else {
+    dS_da = b_x - a_x;
+    gx0 = a * (gxy.x - gxx.x);
+    gx1 = a * (gxy.y - gxx.y);
+  }
+  gx_out[point_at(at) + 0] = gx0;
+  gx_out[point_at(at) + 1] = gx1;
+  galpha_out[at] = dS_da;
+  return a * dS_da;
+}
+
+// Row j of y (potentials b_y: y over y, a_y: y over x; weight w): its term of the debiased cost.
+__device__ __forceinline__ float y_row_term(float b_y, float a_y, float w, const Marginals& m) {
+  if (m.unbalanced) return w * m.w_unb * (expf(-b_y * m.inv_rho) - expf(-a_y * m.inv_rho));
+  return w * (a_y - b_y);
+}
+
 __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
     const float* __restrict__ xs, const float* __restrict__ alpha, const int* __restrict__ s_start,
     const int* __restrict__ s_cnt, const float* __restrict__ yt, const float* __restrict__ beta,
@@ -87,8 +119,6 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
   float* red = reinterpret_cast<float*>(smem_raw + sizeof(WaveLds) * kWaves);  // [kWaves][5]
 
   const int b = blockIdx.x;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
   const int s0 = s_start[b], N = s_cnt[b];
   const int t0 = t_start[b], M = t_cnt[b];
   if (N <= 0 || M <= 0) {          // reference: image skipped (loss_libs.py:25-28)
@@ -101,22 +131,26 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
     if (loss_kp && threadIdx.x < kWaves) loss_kp[b * kWaves + threadIdx.x] = 0.f;
     return;
   }
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   WaveLds& L = all[wave];
   const int k = wave;  // keypoint
 
   float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
   for (int i = lane; i < N; i += 64) {
-    const float x = xs[((size_t)(s0 + i) * 8 + k) * 2 + 0];
-    const float y = xs[((size_t)(s0 + i) * 8 + k) * 2 + 1];
-    const float a = alpha[(size_t)(s0 + i) * 8 + k];
+    const size_t at = weight_at(s0 + i, k);
+    const float x = xs[point_at(at) + 0];
+    const float y = xs[point_at(at) + 1];
+    const float a = alpha[at];
     L.px[i] = x; L.py[i] = y;
     L.la[i] = a > 0.f ? logf(a) : kNegLog;
     mnx = fminf(mnx, x); mxx = fmaxf(mxx, x); mny = fminf(mny, y); mxy = fmaxf(mxy, y);
   }
   for (int j = lane; j < M; j += 64) {
-    const float x = yt[((size_t)(t0 + j) * 8 + k) * 2 + 0];
-    const float y = yt[((size_t)(t0 + j) * 8 + k) * 2 + 1];
-    const float w = beta[(size_t)(t0 + j) * 8 + k];
+    const size_t at = weight_at(t0 + j, k);
+    const float x = yt[point_at(at) + 0];
+    const float y = yt[point_at(at) + 1];
+    const float w = beta[at];
     L.qx[j] = x; L.qy[j] = y;
     L.lb[j] = w > 0.f ? logf(w) : kNegLog;
     mnx = fminf(mnx, x); mxx = fmaxf(mxx, x); mny = fminf(mny, y); mxy = fmaxf(mxy, y);
@@ -161,6 +195,15 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
     s_lam[i] = unbalanced ? (float)(1.0 / (1.0 + e / rho)) : 1.f;
   }
   __syncthreads();
+  // step `it` of the schedule: from the table, or (tabled = false, and past the table's end) in fp64 here
+  auto eps_step = [&](int it, bool tabled) -> EpsStep {
+    if (tabled && it < kSched) return {s_lam[it], s_feps[it], s_inv[it]};
+    const double e = eps_at(it);
+    return {unbalanced ? (float)(1.0 / (1.0 + e / rho)) : 1.f, (float)e, (float)(1.0 / e)};
+  };
+  auto marginals = [&](const EpsStep& last) -> Marginals {
+    return {unbalanced, (float)(rho + 0.5 * eps_at(n_eps - 1)), unbalanced ? (float)(1.0 / rho) : 0.f, last.lam};
+  };
 
   // ---- small sets (N, M <= 16: the KD step has ~10 cells per image): the four softmins of an update run side by
   // side on the four 16-lane rows of the wave instead of one after the other on 10 of its 64 lanes.  Same
@@ -182,21 +225,12 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
     const float ry = act ? (on_x ? L.py[idx] : L.qy[idx]) : 0.f;
     float g0, g1;
     {
-      const double eps = eps_at(0);
-      const float lam = unbalanced ? (float)(1.0 / (1.0 + eps / rho)) : 1.f;
-      const float feps = (float)eps, inv = (float)(1.0 / eps);
+      const auto [lam, feps, inv] = eps_step(0, false);
       if (act) pot[idx] = -lam * feps * lse_row<false>(rx, ry, cxs, cys, from_x ? L.la : L.lb, n_cols, inv, g0, g1);
     }
     __syncthreads();
     for (int it = 0; it < n_eps; ++it) {
-      float lam, feps, inv;
-      if (it < kSched) {
-        lam = s_lam[it]; feps = s_feps[it]; inv = s_inv[it];
-      } else {
-        const double e = eps_at(it);
-        lam = unbalanced ? (float)(1.0 / (1.0 + e / rho)) : 1.f;
-        feps = (float)e; inv = (float)(1.0 / e);
-      }
+      const auto [lam, feps, inv] = eps_step(it, true);
       if (act) hself[idx] = logw[idx] + pot[idx] * inv;
       __syncthreads();
       if (act) {
@@ -205,13 +239,11 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
       }
       __syncthreads();
     }
-    const double eps = eps_at(n_eps - 1);
-    const float lam = unbalanced ? (float)(1.0 / (1.0 + eps / rho)) : 1.f;
-    const float feps = (float)eps, inv = (float)(1.0 / eps);
+    const EpsStep last = eps_step(n_eps - 1, false);
+    const float lam = last.lam, feps = last.feps, inv = last.inv;
     if (act) hself[idx] = logw[idx] + pot[idx] * inv;
     __syncthreads();
-    const float w_unb = (float)(rho + 0.5 * eps);
-    const float inv_rho = unbalanced ? (float)(1.0 / rho) : 0.f;
+    const Marginals marg = marginals(last);
     float gr0 = 0.f, gr1 = 0.f;
     float val = 0.f;
     if (act) {
@@ -221,48 +253,18 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
     // lanes idx (a_x / b_y) and idx + 16 (b_x / a_y) hold the two halves of a row's result
     const float o_val = __shfl_xor(val, 16, 64), o_g0 = __shfl_xor(gr0, 16, 64), o_g1 = __shfl_xor(gr1, 16, 64);
     float part = 0.f;
-    if (grp == 0 && act) {
-      const float a_x = val, b_x = o_val, gxx0 = gr0, gxx1 = gr1, gxy0 = o_g0, gxy1 = o_g1;
-      const float a = alpha[(size_t)(s0 + idx) * 8 + k];
-      float dS_da, gx0, gx1;
-      if (unbalanced) {
-        const float ea = expf(-a_x * inv_rho), eb = expf(-b_x * inv_rho);
-        dS_da = w_unb * (ea - eb);
-        const float c = -a * w_unb * inv_rho * lam;
-        gx0 = c * (ea * gxx0 - eb * gxy0);
-        gx1 = c * (ea * gxx1 - eb * gxy1);
-      } else {
-        dS_da = b_x - a_x;
-        gx0 = a * (gxy0 - gxx0);
-        gx1 = a * (gxy1 - gxx1);
-      }
-      part = a * dS_da;
-      gx_out[((size_t)(s0 + idx) * 8 + k) * 2 + 0] = gx0;
-      gx_out[((size_t)(s0 + idx) * 8 + k) * 2 + 1] = gx1;
-      galpha_out[(size_t)(s0 + idx) * 8 + k] = dS_da;
-    } else if (grp == 2 && act) {
-      const float b_y = val, a_y = o_val;
-      const float w = beta[(size_t)(t0 + idx) * 8 + k];
-      if (unbalanced) part = w * w_unb * (expf(-b_y * inv_rho) - expf(-a_y * inv_rho));
-      else part = w * (a_y - b_y);
-    }
-    part = wave_sum(part);
-    if (lane == 0) { red[wave * 5 + 4] = part; if (loss_kp) loss_kp[b * kWaves + wave] = part; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float tot = 0.f;
-      for (int w = 0; w < kWaves; ++w) tot += red[w * 5 + 4];
-      loss_img[b] = tot;
-      valid_img[b] = 1;
-    }
+    if (grp == 0 && act)
+      part = finish_x_row(val, o_val, {gr0, gr1}, {o_g0, o_g1}, alpha[weight_at(s0 + idx, k)], marg, gx_out, galpha_out,
+                          weight_at(s0 + idx, k));
+    else if (grp == 2 && act)
+      part = y_row_term(val, o_val, beta[weight_at(t0 + idx, k)], marg);
+    small_problem_finish(part, red + 4, loss_img, valid_img, loss_kp, 5);
     return;
   }
 
   // ---- initialisation at eps_0 -------------------------------------------------
   {
-    const double eps = eps_at(0);
-    const float lam = unbalanced ? (float)(1.0 / (1.0 + eps / rho)) : 1.f;
-    const float feps = (float)eps, inv = (float)(1.0 / eps);
+    const auto [lam, feps, inv] = eps_step(0, false);
     float g0, g1;
     for (int i = lane; i < N; i += 64) {
       const float rx = L.px[i], ry = L.py[i];
@@ -279,14 +281,7 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
 
   // ---- epsilon-scaling loop (no gradient) ----------------------------------------
   for (int it = 0; it < n_eps; ++it) {
-    float lam, feps, inv;
-    if (it < kSched) {
-      lam = s_lam[it]; feps = s_feps[it]; inv = s_inv[it];
-    } else {
-      const double e = eps_at(it);
-      lam = unbalanced ? (float)(1.0 / (1.0 + e / rho)) : 1.f;
-      feps = (float)e; inv = (float)(1.0 / e);
-    }
+    const auto [lam, feps, inv] = eps_step(it, true);
     for (int i = lane; i < N; i += 64) {
       L.hx1[i] = L.la[i] + L.ax[i] * inv;
       L.hx2[i] = L.la[i] + L.bx[i] * inv;
@@ -315,9 +310,8 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
   }
 
   // ---- last extrapolation (carries the gradient) + debiased cost -------------------
-  const double eps = eps_at(n_eps - 1);
-  const float lam = unbalanced ? (float)(1.0 / (1.0 + eps / rho)) : 1.f;
-  const float feps = (float)eps, inv = (float)(1.0 / eps);
+  const EpsStep last = eps_step(n_eps - 1, false);
+  const float lam = last.lam, feps = last.feps, inv = last.inv;
   for (int i = lane; i < N; i += 64) {
     L.hx1[i] = L.la[i] + L.ax[i] * inv;
     L.hx2[i] = L.la[i] + L.bx[i] * inv;
@@ -327,50 +321,23 @@ __global__ __launch_bounds__(64 * kWaves) void sinkhorn_small_kernel(
     L.hy2[j] = L.lb[j] + L.ay[j] * inv;
   }
   __syncthreads();
-  const float w_unb = (float)(rho + 0.5 * eps);
-  const float inv_rho = unbalanced ? (float)(1.0 / rho) : 0.f;
+  const Marginals marg = marginals(last);
   float part = 0.f;
   for (int i = lane; i < N; i += 64) {
     const float rx = L.px[i], ry = L.py[i];
-    float gxx0, gxx1, gxy0, gxy1;
-    const float a_x = -lam * feps * lse_row<true>(rx, ry, L.px, L.py, L.hx1, N, inv, gxx0, gxx1);
-    const float b_x = -lam * feps * lse_row<true>(rx, ry, L.qx, L.qy, L.hy2, M, inv, gxy0, gxy1);
-    const float a = alpha[(size_t)(s0 + i) * 8 + k];
-    float dS_da, gx0, gx1;
-    if (unbalanced) {
-      const float ea = expf(-a_x * inv_rho), eb = expf(-b_x * inv_rho);
-      dS_da = w_unb * (ea - eb);
-      const float c = -a * w_unb * inv_rho * lam;
-      gx0 = c * (ea * gxx0 - eb * gxy0);
-      gx1 = c * (ea * gxx1 - eb * gxy1);
-    } else {
-      dS_da = b_x - a_x;
-      gx0 = a * (gxy0 - gxx0);
-      gx1 = a * (gxy1 - gxx1);
-    }
-    part += a * dS_da;
-    gx_out[((size_t)(s0 + i) * 8 + k) * 2 + 0] = gx0;
-    gx_out[((size_t)(s0 + i) * 8 + k) * 2 + 1] = gx1;
-    galpha_out[(size_t)(s0 + i) * 8 + k] = dS_da;
+    float2 gxx, gxy;
+    const float a_x = -lam * feps * lse_row<true>(rx, ry, L.px, L.py, L.hx1, N, inv, gxx.x, gxx.y);
+    const float b_x = -lam * feps * lse_row<true>(rx, ry, L.qx, L.qy, L.hy2, M, inv, gxy.x, gxy.y);
+    part += finish_x_row(a_x, b_x, gxx, gxy, alpha[weight_at(s0 + i, k)], marg, gx_out, galpha_out, weight_at(s0 + i, k));
   }
   for (int j = lane; j < M; j += 64) {
     const float rx = L.qx[j], ry = L.qy[j];
     float g0, g1;
     const float b_y = -lam * feps * lse_row<false>(rx, ry, L.qx, L.qy, L.hy1, M, inv, g0, g1);
     const float a_y = -lam * feps * lse_row<false>(rx, ry, L.px, L.py, L.hx2, N, inv, g0, g1);
-    const float w = beta[(size_t)(t0 + j) * 8 + k];
-    if (unbalanced) part += w * w_unb * (expf(-b_y * inv_rho) - expf(-a_y * inv_rho));
-    else part += w * (a_y - b_y);
+    part += y_row_term(b_y, a_y, beta[weight_at(t0 + j, k)], marg);
   }
-  part = wave_sum(part);
-  if (lane == 0) { red[wave * 5 + 4] = part; if (loss_kp) loss_kp[b * kWaves + wave] = part; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int w = 0; w < kWaves; ++w) tot += red[w * 5 + 4];
-    loss_img[b] = tot;
-    valid_img[b] = 1;
-  }
+  small_problem_finish(part, red + 4, loss_img, valid_img, loss_kp, 5);
 }
 
 }  // namespace
@@ -380,9 +347,9 @@ extern "C" int kd6d_sinkhorn_div_fwd_bwd(const float* xs, const float* alpha, co
                                          const int32_t* t_start, const int32_t* t_cnt, int n_images, float p, float blur, float scaling,
                                          float reach, float* loss_img, int32_t* valid_img, float* loss_kp,
                                          float* grad_xs, float* grad_alpha, void* stream) {
-  KD6D_CHECK_ARG(xs && alpha && s_start && s_cnt && yt && beta && t_start && t_cnt && loss_img && valid_img && grad_xs &&
-                     grad_alpha,
-                 "kd6d_sinkhorn_div_fwd_bwd: null pointer");
+  if (const int rc = check_small_set_pointers("kd6d_sinkhorn_div_fwd_bwd", xs, alpha, s_start, s_cnt, yt, beta, t_start,
+                                              t_cnt, loss_img, valid_img, grad_xs, grad_alpha))
+    return rc;
   KD6D_CHECK_ARG(n_images > 0, "kd6d_sinkhorn_div_fwd_bwd: n_images=%d", n_images);
   if (p != 2.0f) {
     kd6d_set_error("kd6d_sinkhorn_div_fwd_bwd: only p=2 is implemented (got %g)", (double)p);

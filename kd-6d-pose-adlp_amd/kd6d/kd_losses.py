@@ -483,20 +483,16 @@ class KDLoss:
                                   P(pos_row), P(pos_gt), ops._stream()), "kd6d_ssc_assign")
         return dict(rows=rows, levels=tuple(levels), batch=batch, labels=labels, wf=wf, wi=wi, keys=keys)
 
-    def _divergence(self, xs, alpha, start, cnt, teacher, n, loss, valid, g_xs, g_alpha, st):
-        """The KD term's one launch over n problems (student segments start / cnt, the teacher's own): the Sinkhorn
-        divergence, or the kernel distance self.kernel names.  Same buffers, same contract for both."""
-        P = ops._ptr
+    def _divergence(self, xs, alpha, start, cnt, teacher, n, loss, valid, g_xs, g_alpha):
+        """The KD term's one launch over n problems (student segments start / cnt, the teacher's own), on the current
+        stream: the Sinkhorn divergence, or the kernel distance self.kernel names.  Same buffers, same contract for
+        both; the gradient buffers were zeroed by the step prologue (ops adds no fill to the captured step)."""
+        sets = (xs, alpha, start, cnt, teacher.t_kp_norm, teacher.t_beta, teacher.t_start, teacher.t_cnt, n)
+        out = (loss, valid, g_xs, g_alpha)
         if self.kernel is None:
-            check(lib.kd6d_sinkhorn_div_fwd_bwd(P(xs), P(alpha), P(start), P(cnt), P(teacher.t_kp_norm),
-                                                P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), n, self.p,
-                                                self.blur, self.scaling, self.reach, P(loss), P(valid), None,
-                                                P(g_xs), P(g_alpha), st), "kd6d_sinkhorn_div_fwd_bwd")
+            ops.sinkhorn_div(*sets, self.p, self.blur, self.scaling, self.reach, out=out)
         else:       # p, scaling and reach do not enter a kernel distance (geomloss ignores them alike)
-            check(lib.kd6d_kernel_div_fwd_bwd(self.kernel, P(xs), P(alpha), P(start), P(cnt), P(teacher.t_kp_norm),
-                                              P(teacher.t_beta), P(teacher.t_start), P(teacher.t_cnt), n, self.blur,
-                                              P(loss), P(valid), None, P(g_xs), P(g_alpha), st),
-                  "kd6d_kernel_div_fwd_bwd")
+            ops.kernel_div(self.kernel, *sets, self.blur, out=out)
 
     def forward(self, cls_s, reg_s, levels, batch, tgt, teacher, keys=None, seg_scale=None, pre=None):
         dev = cls_s.device
@@ -551,14 +547,14 @@ class KDLoss:
             o_start, o_cnt, o_valid, dest = (part(wi, seg_i, k) for k in ("obj_start", "obj_cnt", "valid_obj", "dest"))
             check(lib.kd6d_kd_group_objects(P(pos_cnt), P(pos_gt), P(xs), P(alpha), batch, cap, P(o_start), P(o_cnt),
                                             P(dest), P(xs_o), P(al_o), st), "kd6d_kd_group_objects")
-            self._divergence(xs_o, al_o, o_start, o_cnt, teacher, nobj, loss_obj, o_valid, g_xs_o, g_al_o, st)
+            self._divergence(xs_o, al_o, o_start, o_cnt, teacher, nobj, loss_obj, o_valid, g_xs_o, g_al_o)
             check(lib.kd6d_kd_mean(P(loss_obj), P(o_valid), nobj, P(losses[2:3]), P(n_valid), st), "kd6d_kd_mean")
             check(lib.kd6d_kd_scatter_objects(P(pos_cnt), P(pos_gt), P(dest), P(o_valid), P(g_xs_o), P(g_al_o), batch,
                                               cap, P(g_xs), P(g_alpha), P(valid), st), "kd6d_kd_scatter_objects")
             self.obj = dict(start=o_start, cnt=o_cnt, valid=o_valid, dest=dest, loss=loss_obj, xs=xs_o, alpha=al_o,
                             g_xs=g_xs_o, g_alpha=g_al_o)
         elif teacher is not None:
-            self._divergence(xs, alpha, s_start, pos_cnt, teacher, batch, loss_img, valid, g_xs, g_alpha, st)
+            self._divergence(xs, alpha, s_start, pos_cnt, teacher, batch, loss_img, valid, g_xs, g_alpha)
             check(lib.kd6d_kd_mean(P(loss_img), P(valid), batch, P(losses[2:3]), P(n_valid), st), "kd6d_kd_mean")
         self.ctx = dict(lv=lv, cls=cls_s, reg=reg_s, labels=labels, pos_cnt=pos_cnt, pos_row=pos_row, pos_gt=pos_gt,
                         tgt=tgt, g_reg=g_reg, g_xs=g_xs, g_alpha=g_alpha, n_valid=n_valid, valid=valid,

@@ -14,12 +14,13 @@ from ..kd_losses import KDLoss, PackedTargets, TeacherKnowledge, check_gtype
 _DENSE_DIMS = (2, 4, 8, 16)
 
 
-class _SinkhornBatchFn(torch.autograd.Function):
-    """(alpha (B,N), x (B,N,D), beta (B,M), y (B,M,D)) -> (B,) divergences, one epsilon schedule for the whole batch
-    (geomloss measures the diameter over all B*(N+M) points).  Gradients reach alpha and x."""
+class _BatchFn(torch.autograd.Function):
+    """(alpha (B,N), x (B,N,D), beta (B,M), y (B,M,D)) -> (B,) losses; gradients reach alpha and x.  small(*sets,
+    loss_kp=) / dense(x, alpha, y, beta, diameter) are the loss's two launches (SamplesLoss.launches); joint: the B
+    problems share one epsilon schedule (geomloss measures the Sinkhorn's diameter over all B*(N+M) points)."""
 
     @staticmethod
-    def forward(ctx, alpha, x, beta, y, p, blur, scaling, reach):
+    def forward(ctx, alpha, x, beta, y, small, dense, joint):
         B, N, D = x.shape
         M = y.shape[1]
         dev = x.device
@@ -29,61 +30,7 @@ class _SinkhornBatchFn(torch.autograd.Function):
         cap = ops.lib.kd6d_sinkhorn_max_points()
         if D == 2 and B <= 8 and N <= cap and M <= cap:
             # one workgroup, one wave per problem; a batch shorter than 8 is filled with copies of problem 0 (same
-            # points: the joint diameter does not move), whose results are dropped
-            idx = torch.arange(8, device=dev) % B if B == 8 else torch.cat(
-                [torch.arange(B, device=dev), torch.zeros(8 - B, dtype=torch.long, device=dev)])
-            xs = xd[idx].permute(1, 0, 2).contiguous()            # (N,8,2)
-            yt = yd[idx].permute(1, 0, 2).contiguous()
-            al = ad[idx].t().contiguous()                         # (N,8)
-            be = bd[idx].t().contiguous()
-            i32 = dict(dtype=torch.int32, device=dev)
-            zero = torch.zeros(1, **i32)
-            loss_kp = torch.empty(1, 8, **f32)
-            _, valid, gx, ga = ops.sinkhorn_div(xs, al, zero, torch.full((1,), N, **i32), yt, be, zero,
-                                                torch.full((1,), M, **i32), 1, p, blur, scaling, reach, loss_kp=loss_kp)
-            out = loss_kp[0, :B].clone()
-            gx, ga = gx.permute(1, 0, 2)[:B].contiguous(), ga.t()[:B].contiguous()
-        elif D in _DENSE_DIMS:
-            pts = torch.cat([xd.reshape(-1, D), yd.reshape(-1, D)], 0)
-            diameter = float((pts.max(0)[0] - pts.min(0)[0]).norm())          # the reference's .item() sync
-            out = torch.empty(B, **f32)
-            gx, ga = torch.empty(B, N, D, **f32), torch.empty(B, N, **f32)
-            for b in range(B):
-                l, g1, g2 = ops.sinkhorn_dense(xd[b].contiguous(), ad[b].contiguous(), yd[b].contiguous(),
-                                               bd[b].contiguous(), blur, scaling, reach, diameter, p)
-                out[b:b + 1].copy_(l)
-                gx[b].copy_(g1)
-                ga[b].copy_(g2)
-        else:
-            raise NotImplementedError("SamplesLoss on the HIP path: D=2 with <= %d points per set, or D in %s for "
-                                      "larger sets (got D=%d)" % (cap, _DENSE_DIMS, D))
-        ctx.save_for_backward(gx, ga)
-        ctx.dtypes = (alpha.dtype, x.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        gx, ga = ctx.saved_tensors
-        adt, xdt = ctx.dtypes
-        return (g[:, None] * ga).to(adt), (g[:, None, None] * gx).to(xdt), None, None, None, None, None, None
-
-
-class _KernelBatchFn(torch.autograd.Function):
-    """(alpha (B,N), x (B,N,D), beta (B,M), y (B,M,D)) -> (B,) kernel distances (kind = a KD6D_KERNEL_* code).
-    Gradients reach alpha and x."""
-
-    @staticmethod
-    def forward(ctx, alpha, x, beta, y, kind, blur):
-        B, N, D = x.shape
-        M = y.shape[1]
-        dev = x.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        xd, yd = x.detach().to(torch.float32), y.detach().to(torch.float32)
-        ad, bd = alpha.detach().to(torch.float32), beta.detach().to(torch.float32)
-        cap = ops.lib.kd6d_kernel_div_max_points()
-        if D == 2 and B <= 8 and N <= cap and M <= cap:
-            # one workgroup, one wave per problem; a batch shorter than 8 is filled with copies of problem 0, whose
-            # results are dropped (the problems are independent: nothing like the Sinkhorn's joint diameter here)
+            # points: a joint diameter does not move), whose results are dropped
             idx = torch.cat([torch.arange(B, device=dev), torch.zeros(8 - B, dtype=torch.long, device=dev)])
             xs = xd[idx].permute(1, 0, 2).contiguous()            # (N,8,2)
             yt = yd[idx].permute(1, 0, 2).contiguous()
@@ -92,16 +39,19 @@ class _KernelBatchFn(torch.autograd.Function):
             i32 = dict(dtype=torch.int32, device=dev)
             zero = torch.zeros(1, **i32)
             loss_kp = torch.empty(1, 8, **f32)
-            _, valid, gx, ga = ops.kernel_div(kind, xs, al, zero, torch.full((1,), N, **i32), yt, be, zero,
-                                              torch.full((1,), M, **i32), 1, blur, loss_kp=loss_kp)
+            _, valid, gx, ga = small(xs, al, zero, torch.full((1,), N, **i32), yt, be, zero, torch.full((1,), M, **i32), 1,
+                                     loss_kp=loss_kp)
             out = loss_kp[0, :B].clone()
             gx, ga = gx.permute(1, 0, 2)[:B].contiguous(), ga.t()[:B].contiguous()
         elif D in _DENSE_DIMS:
+            diameter = None
+            if joint:
+                pts = torch.cat([xd.reshape(-1, D), yd.reshape(-1, D)], 0)
+                diameter = float((pts.max(0)[0] - pts.min(0)[0]).norm())      # the reference's .item() sync
             out = torch.empty(B, **f32)
             gx, ga = torch.empty(B, N, D, **f32), torch.empty(B, N, **f32)
             for b in range(B):
-                l, g1, g2 = ops.kernel_dense(kind, xd[b].contiguous(), ad[b].contiguous(), yd[b].contiguous(),
-                                             bd[b].contiguous(), blur)
+                l, g1, g2 = dense(xd[b].contiguous(), ad[b].contiguous(), yd[b].contiguous(), bd[b].contiguous(), diameter)
                 out[b:b + 1].copy_(l)
                 gx[b].copy_(g1)
                 ga[b].copy_(g2)
@@ -116,7 +66,7 @@ class _KernelBatchFn(torch.autograd.Function):
     def backward(ctx, g):
         gx, ga = ctx.saved_tensors
         adt, xdt = ctx.dtypes
-        return (g[:, None] * ga).to(adt), (g[:, None, None] * gx).to(xdt), None, None, None, None
+        return (g[:, None] * ga).to(adt), (g[:, None, None] * gx).to(xdt), None, None, None, None, None
 
 
 class SamplesLoss:
@@ -137,6 +87,17 @@ class SamplesLoss:
             raise NotImplementedError("SamplesLoss options not implemented on the HIP path: %s" % sorted(unsupported))
         self.loss, self.p, self.blur, self.scaling, self.reach = loss, float(p), float(blur), float(scaling), reach
 
+    def launches(self):
+        """-> (small, dense, joint): the loss's small-set launch small(*sets, loss_kp=None) over ops.sinkhorn_div /
+        ops.kernel_div, its one-problem launch dense(x, alpha, y, beta, diameter), and whether the problems of a batch
+        share one diameter (the Sinkhorn's schedule; the kernel distances' problems are independent)."""
+        if self.kernel is not None:
+            return (lambda *sets, **kw: ops.kernel_div(self.kernel, *sets, self.blur, **kw),
+                    lambda x, a, y, b, diameter: ops.kernel_dense(self.kernel, x, a, y, b, self.blur), False)
+        return (lambda *sets, **kw: ops.sinkhorn_div(*sets, self.p, self.blur, self.scaling, self.reach, **kw),
+                lambda x, a, y, b, diameter: ops.sinkhorn_dense(x, a, y, b, self.blur, self.scaling, self.reach, diameter,
+                                                                self.p), True)
+
     def __call__(self, *args):
         if len(args) == 2:
             x, y = args
@@ -153,10 +114,7 @@ class SamplesLoss:
             raise NotImplementedError("gradients w.r.t. the second measure (beta, y) are not computed on the HIP path")
         if not x.is_cuda:
             raise RuntimeError("kd6d SamplesLoss runs on the GPU only (no CPU fallback)")
-        if self.kernel is not None:
-            out = _KernelBatchFn.apply(alpha, x, beta, y, self.kernel, self.blur)
-        else:
-            out = _SinkhornBatchFn.apply(alpha, x, beta, y, self.p, self.blur, self.scaling, self.reach)
+        out = _BatchFn.apply(alpha, x, beta, y, *self.launches())
         return out[0] if squeeze else out
 
 

@@ -23,10 +23,8 @@ class _PackedSinkhornFn(torch.autograd.Function):
         s_start, t_start = (torch.cumsum(sc, 0) - sc).to(**i32), (torch.cumsum(tc, 0) - tc).to(**i32)
         sets = (xs.detach().contiguous(), alpha.detach().contiguous(), s_start, sc.to(**i32),
                 yt.detach().contiguous(), beta.detach().contiguous(), t_start, tc.to(**i32), len(s_cnt))
-        if kd.kernel is not None:          # SamplesLoss(kernel_losses=True): a kernel distance, same layouts
-            loss, valid, gx, ga = ops.kernel_div(kd.kernel, *sets, kd.blur)
-        else:
-            loss, valid, gx, ga = ops.sinkhorn_div(*sets, kd.p, kd.blur, kd.scaling, kd.reach)
+        small, _dense, _joint = kd.launches()               # the Sinkhorn launch or a kernel distance's, same layouts
+        loss, valid, gx, ga = small(*sets)
         img_of = torch.repeat_interleave(torch.arange(len(s_cnt)), sc.long()).to(dev)
         ctx.save_for_backward(gx, ga, img_of)
         return loss

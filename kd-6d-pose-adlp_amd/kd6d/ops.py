@@ -652,21 +652,30 @@ def image_to_nhwc(img, dtype, cpad=8, out=None):
     return out
 
 
-def sinkhorn_div(xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, p, blur, scaling, reach, loss_kp=None):
-    """xs (P,8,2), alpha (P,8), yt (M,8,2), beta (M,8); image b owns student rows
-    [s_start[b], s_start[b]+s_cnt[b]) and teacher rows likewise (int32 device arrays).
-    Returns loss_img (B), valid_img (B) int32, grad_xs (P,8,2), grad_alpha (P,8); loss_kp: optional (B,8) fp32
-    output of the eight per-keypoint divergences."""
-    dev = xs.device
-    loss = torch.empty(n_images, dtype=torch.float32, device=dev)
-    valid = torch.empty(n_images, dtype=torch.int32, device=dev)
-    gx = torch.zeros_like(xs)
-    ga = torch.zeros_like(alpha)
-    check(lib.kd6d_sinkhorn_div_fwd_bwd(_ptr(xs), _ptr(alpha), _ptr(s_start), _ptr(s_cnt), _ptr(yt), _ptr(beta),
-                                        _ptr(t_start), _ptr(t_cnt), n_images, p, blur, scaling,
-                                        reach if reach is not None else -1.0, _ptr(loss), _ptr(valid), _ptr(loss_kp),
-                                        _ptr(gx), _ptr(ga), _stream()), "kd6d_sinkhorn_div_fwd_bwd")
-    return loss, valid, gx, ga
+def _small_set_div(launch, name, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, loss_kp, out):
+    """One small-set launch (include/kd6d.h, "the small-set launch contract"): xs (P,8,2), alpha (P,8), yt (M,8,2),
+    beta (M,8); problem b owns student rows [s_start[b], s_start[b]+s_cnt[b]) and teacher rows likewise (int32 device
+    arrays).  -> loss_img (B), valid_img (B) int32, grad_xs (P,8,2), grad_alpha (P,8); loss_kp: optional (B,8) fp32 output
+    of the eight per-keypoint values.  out: these four as the caller's buffers, used as they are (the kernel does not
+    write the gradient rows of skipped problems: the caller has zeroed them); otherwise allocated here, gradients zeroed.
+    launch(inputs, outputs) makes the C call with the entry point's own arguments between the two groups."""
+    if out is None:
+        dev = xs.device
+        out = (torch.empty(n_images, dtype=torch.float32, device=dev), torch.empty(n_images, dtype=torch.int32, device=dev),
+               torch.zeros_like(xs), torch.zeros_like(alpha))
+    loss, valid, gx, ga = out
+    check(launch((_ptr(xs), _ptr(alpha), _ptr(s_start), _ptr(s_cnt), _ptr(yt), _ptr(beta), _ptr(t_start), _ptr(t_cnt),
+                  n_images), (_ptr(loss), _ptr(valid), _ptr(loss_kp), _ptr(gx), _ptr(ga), _stream())), name)
+    return out
+
+
+def sinkhorn_div(xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, p, blur, scaling, reach, loss_kp=None,
+                 out=None):
+    """Debiased Sinkhorn divergence per problem (csrc/sinkhorn.hip); arguments and results: _small_set_div."""
+    reach = -1.0 if reach is None else reach
+    return _small_set_div(lambda ins, outs: lib.kd6d_sinkhorn_div_fwd_bwd(*ins, p, blur, scaling, reach, *outs),
+                          "kd6d_sinkhorn_div_fwd_bwd", xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images,
+                          loss_kp, out)
 
 
 def kernel_kind(kind):
@@ -679,21 +688,13 @@ def kernel_kind(kind):
     return int(kind)
 
 
-def kernel_div(kind, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, blur, loss_kp=None):
-    """Kernel distance (gaussian / laplacian / energy MMD, csrc/kernel_loss.hip) per problem, with the layouts of
-    sinkhorn_div: xs (P,8,2), alpha (P,8), yt (M,8,2), beta (M,8); problem b owns student rows
-    [s_start[b], s_start[b]+s_cnt[b]) and teacher rows likewise (int32 device arrays).
-    Returns loss_img (B), valid_img (B) int32, grad_xs (P,8,2), grad_alpha (P,8); loss_kp: optional (B,8) fp32
-    output of the eight per-keypoint distances."""
-    dev = xs.device
-    loss = torch.empty(n_images, dtype=torch.float32, device=dev)
-    valid = torch.empty(n_images, dtype=torch.int32, device=dev)
-    gx = torch.zeros_like(xs)
-    ga = torch.zeros_like(alpha)
-    check(lib.kd6d_kernel_div_fwd_bwd(kernel_kind(kind), _ptr(xs), _ptr(alpha), _ptr(s_start), _ptr(s_cnt), _ptr(yt),
-                                      _ptr(beta), _ptr(t_start), _ptr(t_cnt), n_images, blur, _ptr(loss), _ptr(valid),
-                                      _ptr(loss_kp), _ptr(gx), _ptr(ga), _stream()), "kd6d_kernel_div_fwd_bwd")
-    return loss, valid, gx, ga
+def kernel_div(kind, xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images, blur, loss_kp=None, out=None):
+    """Kernel distance (gaussian / laplacian / energy MMD, csrc/kernel_loss.hip) per problem; arguments and results:
+    _small_set_div."""
+    code = kernel_kind(kind)
+    return _small_set_div(lambda ins, outs: lib.kd6d_kernel_div_fwd_bwd(code, *ins, blur, *outs),
+                          "kd6d_kernel_div_fwd_bwd", xs, alpha, s_start, s_cnt, yt, beta, t_start, t_cnt, n_images,
+                          loss_kp, out)
 
 
 def kernel_dense(kind, x, alpha, y, beta, blur=0.05):

@@ -127,6 +127,108 @@ def test_small_kernel_edge_cases(gpu_device, kind):
     assert bool((gx.cpu()[~w] == 0).all()) and torch.equal(gx.cpu()[w], got["grad_x"][w]) and torch.equal(ga.cpu()[w], got["grad_alpha"][w])
 
 
+# ---- 2b. one contract for both launch families ----------------------------------------------------------------------------
+# (N, M): student-empty, teacher-empty, student / teacher one point over the cap, the smallest problem that runs, the
+# largest the kernels accept (csrc/pointset_small.h)
+CONTRACT_SIZES = [(0, 3), (3, 0), (129, 3), (3, 129), (1, 1), (128, 128)]
+CONTRACT_VALID = [0, 0, -1, -1, 1, 1]
+CONTRACT_SEED = 3                      # the first seed for which small_launch's clamp condition holds on these sizes
+CONTRACT_SINKHORN = {4: "plain_1x1_unb", 5: "plain_128x128_unb"}      # the sinkhorn_cases cases of the two valid problems
+FAMILIES = [("sinkhorn", 0), ("sinkhorn", 1)] + [(k, None) for k in C.KINDS]
+
+
+def _contract_sinkhorn():
+    """The launch of CONTRACT_SIZES from sinkhorn_cases' builders: problems 4 and 5 are its cases plain_1x1_unb and
+    plain_128x128_unb, the skipped ones plain draws; one CANARY row between and around the segments.  -> the arrays of
+    kernel_loss_cases.small_launch, the OT settings, and the cases' fp64 references."""
+    import sinkhorn_cases as S
+    parts, ot = [], None
+    for p, (N, M) in enumerate(CONTRACT_SIZES):
+        if p in CONTRACT_SINKHORN:
+            i = S.inputs(CONTRACT_SINKHORN[p])
+            assert (i["case"].N, i["case"].M) == (N, M)
+            settings = dict(blur=i["blur"], scaling=i["scaling"], reach=i["reach"])
+            assert ot in (None, settings), "the two cases share one launch: they must share its OT settings"
+            ot = settings
+            parts.append((i["xs"], i["al"], i["yt"], i["be"]))
+        else:
+            x, a, y, b = S.draw(max(N, 1), max(M, 1), "unb", 1000 + p)
+            parts.append((x[:N], a[:N], y[:M], b[:M]))
+
+    def lay(pts, wts):
+        start, row = [], 1
+        for q in pts:
+            start.append(row)
+            row += q.shape[0] + 1
+        P_, W_ = torch.full((row, 8, 2), C.CANARY), torch.full((row, 8), C.CANARY)
+        for s, q, w in zip(start, pts, wts):
+            P_[s:s + q.shape[0]], W_[s:s + q.shape[0]] = torch.from_numpy(q.copy()), torch.from_numpy(w.copy())
+        return P_, W_, torch.tensor(start, dtype=torch.int32), torch.tensor([q.shape[0] for q in pts], dtype=torch.int32)
+
+    xs, alpha, s_start, s_cnt = lay([q[0] for q in parts], [q[1] for q in parts])
+    yt, beta, t_start, t_cnt = lay([q[2] for q in parts], [q[3] for q in parts])
+    return (dict(xs=xs, alpha=alpha, s_start=s_start, s_cnt=s_cnt, yt=yt, beta=beta, t_start=t_start, t_cnt=t_cnt), ot,
+            {p: S.reference(n) for p, n in CONTRACT_SINKHORN.items()})
+
+
+@pytest.mark.parametrize("family,lanes", FAMILIES, ids=["%s%s" % (f, "" if l is None else "-lanes%d" % l) for f, l in FAMILIES])
+def test_both_launch_families_honour_one_contract(gpu_device, family, lanes):
+    """ops.sinkhorn_div (16-lane path on and off) and ops.kernel_div on one launch of an empty student set, an empty
+    teacher set, 129 points on either side, 1x1 and 128x128: valid = 0 / -1 / 1; loss_img and the loss_kp row of a skipped
+    problem exactly 0, its gradient rows (and the gaps) as the caller left them; loss_img of a valid problem = its
+    loss_kp row added in index order, bit for bit; the valid problems' values within the bounds of their case files."""
+    import sinkhorn_cases as S
+    _, ops, _ = _kd()
+    dev = gpu_device
+    if family == "sinkhorn":
+        L, ot, refs = _contract_sinkhorn()
+    else:
+        L = C.small_launch(CONTRACT_SIZES, CONTRACT_SEED)
+        ref = C.small_results(L, lambda a, x, b, y: C.reference(a, x, b, y, family, KD_BLUR))
+    P = len(CONTRACT_SIZES)
+    f32 = dict(dtype=torch.float32, device=dev)
+    d = {k: L[k].to(dev) for k in ("xs", "alpha", "s_start", "s_cnt", "yt", "beta", "t_start", "t_cnt")}
+    out = (torch.full((P,), C.CANARY, **f32), torch.full((P,), SENT_I, dtype=torch.int32, device=dev),
+           torch.full(tuple(L["xs"].shape), C.CANARY, **f32), torch.full(tuple(L["alpha"].shape), C.CANARY, **f32))
+    loss_kp = torch.full((P, 8), C.CANARY, **f32)
+    sets = (d["xs"], d["alpha"], d["s_start"], d["s_cnt"], d["yt"], d["beta"], d["t_start"], d["t_cnt"], P)
+    if family == "sinkhorn":
+        ops.set_option("sinkhorn.lanes", lanes)
+        try:
+            got = ops.sinkhorn_div(*sets, 2.0, ot["blur"], ot["scaling"], ot["reach"], loss_kp=loss_kp, out=out)
+        finally:
+            ops.set_option("sinkhorn.lanes", 1)
+    else:
+        got = ops.kernel_div(family, *sets, KD_BLUR, loss_kp=loss_kp, out=out)
+    torch.cuda.synchronize()
+    assert all(g is o for g, o in zip(got, out)), "out= buffers are returned as they are"
+    loss_img, valid, gx, ga = (t.cpu() for t in out)
+    loss_kp = loss_kp.cpu()
+    assert valid.tolist() == CONTRACT_VALID
+    written = torch.zeros(L["xs"].shape[0], dtype=torch.bool)
+    for p, (N, M) in enumerate(CONTRACT_SIZES):
+        s0 = int(L["s_start"][p])
+        if CONTRACT_VALID[p] != 1:
+            assert float(loss_img[p]) == 0.0 and bool((loss_kp[p] == 0).all()), "problem %d: loss of a skipped problem" % p
+            continue
+        written[s0:s0 + N] = True
+        assert float(loss_img[p]) == _fp32_sum_in_order(loss_kp[p]), "problem %d: loss_img is the ordered fp32 sum" % p
+        what = "contract %dx%d" % (N, M)
+        if family == "sinkhorn":
+            mine = dict(loss_kp=loss_kp[p], loss_img=loss_img[p], gx=gx[s0:s0 + N], ga=ga[s0:s0 + N])
+            for o in S.OUTPUTS:
+                limit = S.bound(S.group(S.CASES[CONTRACT_SINKHORN[p]]), o) * float(np.abs(refs[p][o]).max())
+                err = float(np.abs(mine[o].double().numpy() - refs[p][o]).max())
+                print("  sinkhorn lanes %d %-8s %-16s max|err| %.3e  limit %.3e" % (lanes, o, what, err, limit))
+                assert err <= limit, (p, o, err, limit)
+        else:
+            C.assert_within(loss_kp[p], ref["loss"][p], family, "loss", what + " loss_kp")
+            C.assert_within(ga[s0:s0 + N], ref["grad_alpha"][s0:s0 + N], family, "grad_alpha", what)
+            C.assert_within(gx[s0:s0 + N], ref["grad_x"][s0:s0 + N], family, "grad_x", what)
+    assert int(written.sum()) == 129
+    assert bool((gx[~written] == C.CANARY).all()) and bool((ga[~written] == C.CANARY).all()), "a skipped row was written"
+
+
 # ---- 3. independence ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", C.KINDS)
 def test_small_kernel_problems_are_independent(gpu_device, kind):
