@@ -129,6 +129,9 @@ int kd6d_conv2d_pair_pending(void);   /* launches recorded so far in the open br
  * epilogue, so that the normalisation that follows needs no separate reduction pass:
  *   stats_groups == 0: {sum[cout], sumsq[cout]}           (BatchNorm batch statistics, = kd6d_colstats)
  *   stats_groups  > 0: {sum, sumsq} per (level, image, group), the layout kd6d_gn_relu_fwd consumes.
+ *     Refused (KD6D_ERR_UNSUPPORTED / invalid argument, nothing launched): a pixel tile that spans more (level, image)
+ *     keys than the kernel's LDS table holds (1 x 1 levels at a batch above ~60), and a level of H * W % 16 != 0 unless
+ *     cout / 4 (cout / 8 for a bf16 y) divides 256 (conv_plan.h: stats_table_fits, stats_followup_ok).
  * workspace (optional device scratch, any contents): lets layers with few output tiles and a long K run
  * split-K (fp32 partial slabs + a finalize launch); without it they run as one pass. */
 int kd6d_conv2d_fwd(const kd6d_conv_geom* g, int dtype, const void* x,

@@ -1444,7 +1444,13 @@ int dispatch_fwd(const ConvParams& p, const kd6d_conv_geom* g, int dtype, bool x
                  hipStream_t st, const char* who) {
   kd6d_conv::Flags f = plan_flags(p, dtype);
   f.xf = xf; f.has_workspace = workspace != nullptr; f.ws_bytes = workspace_bytes;
-  const FwdPlan pl = kd6d_conv::plan_fwd(plan_shape(g, p.M, p.N, p.C, p.K), f, plan_options(), cached_cu_count());
+  const kd6d_conv::Shape shape = plan_shape(g, p.M, p.N, p.C, p.K);
+  const FwdPlan pl = kd6d_conv::plan_fwd(shape, f, plan_options(), cached_cu_count());
+  if (p.stats && p.stats_groups > 0 && !kd6d_conv::stats_table_fits(shape, pl, p.stats_groups)) {
+    kd6d_set_error("%s: group statistics: a %d-pixel tile spans more (level, image) keys than its LDS table holds (%d)", who,
+                   pl.BP, kd6d_conv::stats_table_max_keys(pl, p.N, p.stats_groups));
+    return KD6D_ERR_UNSUPPORTED;
+  }
   return launch_conv(pl, p, reinterpret_cast<float*>(workspace), st, who);
 }
 
@@ -1517,6 +1523,9 @@ extern "C" int kd6d_conv2d_fwd(const kd6d_conv_geom* g, int dtype, const void* x
   if (stats) {
     rc = set_stats(g, p, stats, stats_groups, "kd6d_conv2d_fwd");
     if (rc) return rc;
+    KD6D_CHECK_ARG(p.stats_skip == 0 || kd6d_conv::stats_followup_ok(g->cout, stats_groups, p.out_f32 || dtype == KD6D_F32),
+                   "kd6d_conv2d_fwd: group statistics of a level that is no whole number of 16-pixel fragments need cout / %d "
+                   "to divide 256 (cout=%d, groups=%d)", (p.out_f32 || dtype == KD6D_F32) ? 4 : 8, g->cout, stats_groups);
   }
   const int pending = kd6d_conv2d_pair_pending();
   rc = dispatch_fwd(p, g, dtype, false, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), "kd6d_conv2d_fwd");

@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "norm_plan.h"
+
 namespace kd6d_conv {
 
 // ---- constants the rules share with the kernels and entry points -----------------------------------------------
@@ -420,6 +422,63 @@ inline bool stats_groups_ok(int cout, int groups) {
 // group statistics: bit s set = level s is NOT summed by the epilogue, which sums whole 16-row fragments that lie inside
 // one image (dst_hw, m_begin: pixels of the level's destination grid and its first GEMM row)
 inline bool stats_level_skipped(int dst_hw, int m_begin) { return (dst_hw % 16) != 0 || (m_begin % 16) != 0; }
+// ... such levels are summed from the stored tensor by a gn_stats launch behind the convolution (stats_followup), which has
+// channel rules of its own (norm_plan.h: cout / 4 -- cout / 8 for a bf16 tensor -- divides 256): kd6d_conv2d_fwd refuses a
+// call with a skipped level that the follow-up would not take, before it launches anything
+inline bool stats_followup_ok(int cout, int groups, bool dst_f32) { return kd6d_norm::gn_stats_levels_ok(cout, groups, !dst_f32); }
+
+// Group statistics, the LDS image of conv_epilogue_stats in the kernel's dead staging memory: the accumulator table
+// [key of the tile][group of the channel tile] of {sum, sumsq}, 16 bytes each, the staged entries (one f32x2 per 4-channel
+// slice of a 16-row fragment: BP * BC / 64 of them) and one key per fragment row.  `nkeys` counts EVERY (level, image) key
+// between the tile's first and last row, the levels the epilogue skips included.
+inline long long stats_table_bytes(int BP, int BC, int cpg_shift, int nkeys) {
+  return (long long)nkeys * (BC >> cpg_shift) * 32 + (long long)BP * BC / 8 + BP / 4;
+}
+// pixels of level i's destination grid (forward sense)
+inline int out_pixels(const Shape& s, int i) {
+  return ((s.seg[i].in_h + 2 * s.pad - s.ks) / s.stride + 1) * ((s.seg[i].in_w + 2 * s.pad - s.ks) / s.stride + 1);
+}
+// (level, image) key of forward GEMM row m: the host form of the kernels' stats_key
+inline int stats_row_key(const Shape& s, int m) {
+  int key = 0;
+  for (int i = 0, mb = 0; i < s.nseg; ++i) {
+    const int hw = out_pixels(s, i);
+    if (m >= mb) key = i * s.batch + (m - mb) / hw;
+    mb += s.batch * hw;
+  }
+  return key;
+}
+// the most keys any tile of BP rows touches.  First the bound of a window of BP rows laid anywhere (at most
+// ceil((BP - 1) / hw) + 1 images of a level, every level at once); the walk over the tiles only where that is not enough
+inline int stats_tile_keys(const Shape& s, int BP, int enough) {
+  int bound = 0;
+  for (int i = 0; i < s.nseg; ++i) {
+    const int hw = out_pixels(s, i), span = (BP + hw - 2) / hw + 1;
+    bound += span < s.batch ? span : s.batch;
+  }
+  if (bound <= enough) return bound;
+  int most = 0;
+  for (int m0 = 0; m0 < s.M; m0 += BP) {
+    const int m_last = (m0 + BP < s.M ? m0 + BP : s.M) - 1;
+    const int n = stats_row_key(s, m_last) - stats_row_key(s, m0) + 1;
+    if (n > most) most = n;
+  }
+  return most;
+}
+// keys per tile the planned kernel's LDS takes with `groups` groups over N channels
+inline int stats_table_max_keys(const FwdPlan& pl, int N, int groups) {
+  const int cs = N / groups == 8 ? 3 : 2;
+  const long long room = pl.lds_bytes - stats_table_bytes(pl.BP, pl.BC, cs, 0);
+  return room <= 0 ? 0 : (int)(room / ((pl.BC >> cs) * 32));
+}
+// Does the table of every tile of the planned launch fit?  The entry points refuse a launch where it does not (small
+// levels at a large batch: a 128 x 128 tile over 1 x 1 levels of 62 or more images).  A fused GroupNorm launch
+// (norm_fusable) has whole levels only, 16 pixels or more per key: at most BP / 16 + 1 keys, which fit every kernel.
+inline bool stats_table_fits(const Shape& s, const FwdPlan& pl, int groups) {
+  if (groups <= 0) return true;
+  const int room = stats_table_max_keys(pl, s.N, groups);
+  return stats_tile_keys(s, pl.BP, room) <= room;
+}
 
 // Would kd6d_conv2d_fwd_norm take the fused path?  `fuse_norm`: option conv.fuse_norm (bit 0 = GroupNorm launches,
 // bit 1 = BatchNorm launches).  The plan of the call as kd6d_conv2d_fwd_norm makes it, then the residency rule of

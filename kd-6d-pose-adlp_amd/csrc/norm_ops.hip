@@ -1532,8 +1532,7 @@ int kd6d_detail::gn_stats_levels(int src_f32, const void* y, const int* row0, co
                                  int G, unsigned mask, long long* stats, hipStream_t st) {
   KD6D_CHECK_ARG(y && stats && nseg >= 1 && nseg <= KD6D_MAX_SEG && batch >= 1 && G >= 1 && G <= 64 && C % G == 0,
                  "gn_stats_levels: bad arguments");
-  const int eg = granule_width(!src_f32);
-  KD6D_CHECK_ARG(channels_ok(C, eg) && (C / G) * 2 >= eg, "gn_stats_levels: C=%d G=%d", C, G);
+  KD6D_CHECK_ARG(gn_stats_levels_ok(C, G, !src_f32), "gn_stats_levels: C=%d G=%d", C, G);
   GnGeom gm;
   gm.nseg = nseg; gm.batch = batch; gm.C = C; gm.G = G;
   gm.chunk_rows = gn_chunk_rows();

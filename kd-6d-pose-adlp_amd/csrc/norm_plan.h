@@ -28,6 +28,11 @@ inline int gn_chunk_rows() { return 128; }
 inline int granule_width(bool bf16) { return bf16 ? 8 : 4; }
 // BatchNorm / GroupNorm / pooled entry points: thread t owns channel granule t % (C/eg) for the whole launch
 inline bool channels_ok(int C, int eg) { return C > 0 && C % eg == 0 && C / eg <= kThreads && kThreads % (C / eg) == 0; }
+// gn_stats_levels (the group statistics of the levels a convolution epilogue leaves out): whole granules inside a pair of groups
+inline bool gn_stats_levels_ok(int C, int G, bool src_bf16) {
+  const int eg = granule_width(src_bf16);
+  return G >= 1 && G <= 64 && C % G == 0 && channels_ok(C, eg) && (C / G) * 2 >= eg;
+}
 // colstats (row-tiled ownership): any C of up to 256 granules
 inline bool colstats_channels_ok(int C, int eg) { return C > 0 && C % eg == 0 && C / eg <= kThreads; }
 

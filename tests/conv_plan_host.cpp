@@ -18,6 +18,13 @@ Options options_of(const int* v) {
   o.tile = v[6]; o.wgrad_small = v[7];
   return o;
 }
+Flags flags_of(const int* flags, long long ws_bytes) {
+  Flags f;
+  f.dtype = flags[0]; f.has_stats = flags[1] != 0; f.stats_groups = flags[2]; f.stats_replicas = flags[3];
+  f.norm_fused = flags[4] != 0; f.xf = flags[5] != 0; f.has_workspace = flags[6] != 0; f.pair_active = flags[7] != 0;
+  f.ws_bytes = ws_bytes;
+  return f;
+}
 }  // namespace
 
 extern "C" {
@@ -25,10 +32,7 @@ extern "C" {
 // out = {family, BP, BC, WP, WC, NSTAGE, HMAX, CG, NB, PDB, NORM, XF, grid_x, grid_y, threads, lds_bytes, n_ctiles, n_ptiles,
 //        p_fastest, nk_split, nsplit, finalize_grid, halo, total_rows, patch_bytes, wbytes, fused_epilogue}
 void cp_plan_conv(const int* shape, const int* flags, long long ws_bytes, const int* opts, int ncu, int dgrad, long long* out) {
-  Flags f;
-  f.dtype = flags[0]; f.has_stats = flags[1] != 0; f.stats_groups = flags[2]; f.stats_replicas = flags[3];
-  f.norm_fused = flags[4] != 0; f.xf = flags[5] != 0; f.has_workspace = flags[6] != 0; f.pair_active = flags[7] != 0;
-  f.ws_bytes = ws_bytes;
+  const Flags f = flags_of(flags, ws_bytes);
   const FwdPlan p = dgrad ? plan_dgrad(shape_of(shape), f, options_of(opts), ncu) : plan_fwd(shape_of(shape), f, options_of(opts), ncu);
   const long long v[27] = {p.family, p.BP, p.BC, p.WP, p.WC, p.NSTAGE, p.HMAX, p.CG, p.NB, p.PDB, p.NORM, p.XF, p.grid_x, p.grid_y,
                            p.threads, p.lds_bytes, p.n_ctiles, p.n_ptiles, p.p_fastest, p.nk_split, p.nsplit, p.finalize_grid,
@@ -46,6 +50,24 @@ void cp_plan_wgrad(const int* shape, int dtype, int with_bias, const int* opts, 
                            p.lds_bytes, p.R, p.tiles_per_img, p.ntiles, p.buf_bytes, p.prow};
   for (int i = 0; i < 19; ++i) out[i] = v[i];
 }
+// the group-statistics table of the forward launch planned for (shape, flags): flags[2] groups
+// out = {keys per tile the planned kernel's LDS holds, most keys any tile touches (the walk), stats_table_fits,
+//        bytes of the table at that many keys, the plan's lds_bytes}
+void cp_stats_table(const int* shape, const int* flags, const int* opts, int ncu, long long* out) {
+  const Shape s = shape_of(shape);
+  const Flags f = flags_of(flags, 0);
+  const FwdPlan p = plan_fwd(s, f, options_of(opts), ncu);
+  const int cs = s.N / f.stats_groups == 8 ? 3 : 2;
+  out[0] = stats_table_max_keys(p, s.N, f.stats_groups);
+  out[1] = stats_tile_keys(s, p.BP, -1);
+  out[2] = stats_table_fits(s, p, f.stats_groups);
+  out[3] = stats_table_bytes(p.BP, p.BC, cs, (int)out[1]);
+  out[4] = p.lds_bytes;
+}
+int cp_stats_row_key(const int* shape, int m) { return stats_row_key(shape_of(shape), m); }
+int cp_stats_level_skipped(int dst_hw, int m_begin) { return stats_level_skipped(dst_hw, m_begin); }
+int cp_stats_followup_ok(int cout, int groups, int dst_f32) { return stats_followup_ok(cout, groups, dst_f32 != 0); }
+int cp_stats_groups_ok(int cout, int groups) { return stats_channels_ok(cout) && stats_groups_ok(cout, groups); }
 int cp_norm_fusable(const int* shape, const int* out_hw, int dtype, int kind, int groups, int fuse_norm, int pair_active,
                     const int* opts, int ncu) {
   return norm_fusable(shape_of(shape), out_hw, dtype, kind, groups, fuse_norm, pair_active != 0, options_of(opts), ncu);

@@ -95,6 +95,19 @@ def fusable(lib, layer, dtype, kind, groups, fuse_norm=3, pair=0, **opts):
     return lib.cp_norm_fusable(layer.shape("fwd"), _ints(layer.out_hw), dtype, kind, groups, fuse_norm, pair, _opts(opts), NCU)
 
 
+def stats_table(lib, layer, dtype, groups, norm=0, ncu=NCU, **opts):
+    """The group-statistics LDS table of the forward launch planned for the layer (conv_plan.h stats_table_*): room = keys
+    per tile the planned kernel holds, tile_keys = the most (level, image) keys any of its tiles touches, fits, bytes, lds."""
+    out = (LL * 5)()
+    lib.cp_stats_table(layer.shape("fwd"), _ints([dtype, 1, groups, 0, norm, 0, 0, 0]), _opts(opts), ncu, out)
+    return Plan(zip("room tile_keys fits bytes lds".split(), out))
+
+
+def stats_row_key(lib, layer, m):
+    """level * batch + image of forward GEMM row m (conv_plan.h stats_row_key, the host form of the kernels' stats_key)."""
+    return lib.cp_stats_row_key(layer.shape("fwd"), m)
+
+
 def variants(lib, name):
     """The rows of the KD6D_CONV_*_TILES list `name` (LISTS), as tuples of 6 ints with the unused columns 0."""
     buf = (ctypes.c_int * (6 * 64))()

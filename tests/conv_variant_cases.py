@@ -14,7 +14,13 @@ Two passes per row:
            where the kernel stores bf16).  No tolerance.
   random   Gaussian inputs rounded to the dtype, built and compared as test_conv_fwd_plain / test_conv_dgrad /
            test_conv_wgrad of tests/test_kernels_gpu.py do: catches what integers cannot (a lost low mantissa bit, a
-           wrong rounding on the store)."""
+           wrong rounding on the store).
+
+Every forward row also runs the fused per-channel statistics on NARROW integers (activations and weights of {-1, 0, 1}, an
+integer shift): with |y| <= 255 the sum of squares over the 256 rows of the tallest tile stays below 2^24, every fp32
+partial a workgroup forms is exact, and the accumulators (fixed point, unit 2^-32, two int64 words) are compared to the
+word with the integer sums of the fp64 reference.  STAT_ROWS holds the rows of the group statistics and of the fused
+instantiations (NORM, XF, the fused-normalisation halo tiles), compared the same way."""
 import collections
 import functools
 
@@ -24,24 +30,23 @@ import torch.nn.functional as F
 import conv_plan_lib as P
 from util_pack import round_to
 
-Row = collections.namedtuple("Row", "id list variant kind dtype options case budgets note")
+Row = collections.namedtuple("Row", "id list variant kind dtype options case budgets note extra why", defaults=({}, ()))
 
 # the lists whose variants serve forward and data gradient / forward only / the weight gradient
 DIRECTIONS = {"igemm": ("fwd", "dgrad"), "glds": ("fwd", "dgrad"), "smallc": ("fwd", "dgrad"), "halo": ("fwd", "dgrad"),
               "splitk": ("fwd",), "wgrad": ("wgrad",), "wgrad_tr": ("wgrad",), "wgrad_small": ("wgrad",)}
 DTYPES = {"igemm": ("bf16", "f32"), "glds": ("bf16",), "smallc": ("bf16",), "halo": ("bf16",), "splitk": ("bf16",),
           "wgrad": ("f32",), "wgrad_tr": ("bf16",), "wgrad_small": ("bf16",)}
-# KD6D_CONV_HALO_NORM_TILES (the NORM instantiations) keep their own tests: test_conv_fwd_norm_*
-OUT_OF_SCOPE = ("halo_norm",)
 # taken on trust from tests/test_kernels_gpu.py::test_conv_halo_two_per_cu_variants (conv.halo = 11 ... 15), which runs
-# forward, data gradient and fused statistics of exactly these five single-patch-buffer twins
+# forward, data gradient and fused statistics of exactly these five single-patch-buffer twins (plain forward and data
+# gradient only: their per-channel and group statistics have exact rows of their own in STAT_ROWS)
 HALO_TWINS = ((128, 128, 2, 2, 33, 0), (128, 128, 4, 2, 33, 0), (128, 64, 4, 2, 33, 0), (64, 64, 4, 2, 33, 0),
               (128, 32, 4, 1, 33, 0))
 
 ROWS = []
 
 
-def _row(lst, variant, kind, dtype, options, case, budgets=(0,), note=""):
+def _make_row(lst, variant, kind, dtype, options, case, budgets=(0,), note=""):
     variant = tuple(variant) + (0,) * (6 - len(variant))
     opt = ",".join("%s=%d" % (k.split(".")[1], v) for k, v in sorted(options.items())) or "default"
     B, cin, cout, k, stride, levels = case
@@ -49,9 +54,13 @@ def _row(lst, variant, kind, dtype, options, case, budgets=(0,), note=""):
                                                 "_".join("%dx%d" % l for l in levels))
     if budgets != (0,):
         rid += "-cu" + "_".join(str(b) for b in budgets)
-    assert all(r.id != rid for r in ROWS), rid
-    ROWS.append(Row(rid, lst, variant, kind, dtype, dict(options), (B, cin, cout, k, stride, [tuple(l) for l in levels]),
-                    tuple(budgets), note))
+    return Row(rid, lst, variant, kind, dtype, dict(options), (B, cin, cout, k, stride, [tuple(l) for l in levels]), tuple(budgets), note)
+
+
+def _row(*args, **kw):
+    r = _make_row(*args, **kw)
+    assert all(q.id != r.id for q in ROWS), r.id
+    ROWS.append(r)
 
 
 # ---- register-staged kernel: 7 tiles x forward / data gradient x bf16 / fp32 -----------------------------------------
@@ -161,7 +170,123 @@ for _bn, _c in WGRAD_CASES:
     _row("wgrad_tr", (_bn,) + ((2, 2) if _bn == 128 else (1, 4)), "wgrad", "bf16", {"wgrad.small": 0}, _c)
     _row("wgrad", {16: (16, 128, 1, 4), 32: (32, 128, 1, 4), 64: (64, 64, 2, 2), 128: (128, 128, 2, 2)}[_bn], "wgrad", "f32", {}, _c)
 
-BY_ID = {r.id: r for r in ROWS}
+# ======== the fused statistics and the fused forms of the forward kernels: STAT_ROWS ==================================
+# kinds:  fwd_gstats  kd6d_conv2d_fwd with group statistics (extra: groups), {sum, sumsq} per (level, image, group)
+#         fwd_norm    kd6d_conv2d_fwd_norm (extra: norm = "group" | "batch", groups): the NORM instantiations
+#         fwd_block   kd6d_conv2d_fwd_block(bn = NULL, stats_replicas = R > 1): NORM = true register-staged tiles
+#         fwd_xf      kd6d_conv2d_fwd_block(bn given) behind an exact 1x1 block A of 8 channels: XF = true tiles
+# Levels the epilogue sums have H * W % 16 == 0 and a first row % 16 == 0 (conv_plan.h stats_level_skipped); the others come
+# from the follow-up launch, which takes cout / 4 (cout / 8 for a bf16 tensor) dividing 256 only (conv_plan.h
+# stats_followup_ok): the rows with a skipped level have 16, 32 or 64 result channels, the channel tails sit in rows of whole
+# levels, and one row records the refusal.  Both kinds of level are compared exactly.
+STAT_ROWS = []
+STAT_KINDS = ("fwd_gstats", "fwd_norm", "fwd_block", "fwd_xf")
+REPLICAS = 3             # replica rows of the fwd_block / fwd_xf rows: workgroup b adds to row b % 3
+
+
+# what a row is there for (Row.why); the host test computes each on the row and holds the table against its own list
+MIXED = ("summed and skipped levels", "M tail, partial fragment")
+TAIL, KEYS, LEVELS, SHORT = "channel tail", "several summed keys in a tile", "a tile across a level boundary", "short last tile"
+
+
+def _stat_row(lst, variant, kind, dtype, options, case, note="", why=(), **extra):
+    r = _make_row(lst, variant, kind, dtype, options, case, note=note)
+    rid = r.id + "".join("-%s%s" % (k[0], v) for k, v in sorted(extra.items()))
+    assert all(q.id != rid for q in STAT_ROWS), rid
+    STAT_ROWS.append(r._replace(id=rid, extra=dict(extra), why=(why,) if isinstance(why, str) else tuple(why)))
+
+
+TINY_PYRAMID = [(8, 8), (4, 4), (2, 2), (1, 1)]      # at a batch of 4: first rows 0, 256, 320, 336; 2x2 and 1x1 are skipped
+# ---- group statistics, register-staged kernel: every tile in bf16 and fp32 ------------------------------------------------
+IGEMM_GSTATS = [
+    # 518 tiles of 256 pixels, the last one 128 rows short; 3 groups of 4 in a 16-channel tile
+    ((256, 16, 4, 1), (1, 8, 12, 3, 1, [(368, 360)]), 3, (TAIL, SHORT)),
+    # summed and skipped levels in one launch, 170 rows: a partial last fragment
+    ((64, 16, 4, 1), (2, 24, 16, 3, 1, TINY_PYRAMID), 4, MIXED),
+    ((256, 32, 4, 1), (1, 8, 24, 3, 1, [(368, 360)]), 3, (TAIL, SHORT)),  # 8 channels per group, 3 of 4 groups
+    # rows 64 ... 127: the last image of level 0 and two images of level 1 in one tile
+    ((64, 32, 4, 1), (3, 8, 24, 3, 1, [(4, 8), (4, 4)]), 6, (LEVELS, KEYS, TAIL)),
+    ((128, 64, 2, 2), (12, 8, 40, 3, 1, [(69, 64)]), 10, (KEYS, "N <= 64")),   # 34.5 tiles per image: tiles in two images
+    ((128, 64, 2, 2), (1, 64, 136, 1, 1, [(129, 128)]), 17, (TAIL, "N > 64")),   # 130 x 3 tiles, the last with one group of 8
+    # tile 4 holds the four 4x4 images, tile 5 only skipped levels and the M tail
+    ((64, 64, 2, 2), (4, 16, 64, 3, 1, TINY_PYRAMID), 8, MIXED + (KEYS,)),
+    ((64, 64, 2, 2), (3, 16, 40, 3, 1, [(8, 8), (4, 4)]), 5, (TAIL,)),   # 5 of 8 groups of 8 in a 64-channel tile
+    ((128, 128, 2, 2), (4, 8, 200, 3, 1, [(88, 70)]), 50, (KEYS, TAIL)),  # 48.125 tiles per image, 18 of 32 groups in the last tile
+]
+for _dtype, _opts in (("bf16", PLAIN), ("f32", {})):
+    for _v, _c, _g, _why in IGEMM_GSTATS:
+        _stat_row("igemm", _v, "fwd_gstats", _dtype, _opts, _c, why=_why, groups=_g)
+
+# ---- ... LDS-DMA kernel --------------------------------------------------------------------------------------------------
+GLDS_GSTATS = [((4, 24, 64, 3, 1, TINY_PYRAMID), 16, MIXED),             # 4 per group; 16 of 32 groups in a 128-channel tile
+               ((3, 64, 136, 1, 1, [(4, 8), (4, 4)]), 17, (LEVELS, TAIL))]   # 8 per group; a tile across the level boundary
+for _t, _v in GLDS_TILE.items():
+    for _c, _g, _why in GLDS_GSTATS:
+        _stat_row("glds", _v, "fwd_gstats", "bf16", {"conv.halo": 0, "conv.smallc": 0, "conv.tile": _t}, _c, why=_why, groups=_g)
+
+# ---- ... halo-patch kernel: every tile of the list, the five twins (conv.halo = 11 ... 15) included -------------------------
+# rows 360 (first rows 0, 320, 352) and 616 (0, 576, 608): the 1 x 4 level is skipped, the last fragment partial; without
+# it 352 and 608 rows of whole levels
+HALO_GSTATS_LEVELS = {65: [(4, 40), (2, 8), (1, 4)], 81: [(4, 72), (2, 8), (1, 4)]}
+HALO_TWIN_PICK = {11: (128, 128, 2, 2), 12: (128, 128, 4, 2), 13: (128, 64, 4, 2), 14: (64, 64, 4, 2), 15: (128, 32, 4, 1)}
+
+
+def _halo_gstats_case(narrow, batch, levels, i):
+    """(case, groups) of the i-th tile of a list: even i a pyramid with skipped levels and 64 (32 for the 32-channel tile)
+    result channels, odd i its whole levels with a channel tail, 136 (24) channels; groups of 4 and of 8 in turn."""
+    if i % 2 == 0:
+        cout = 32 if narrow else 64
+        return (batch, 64, cout, 3, 1, levels), cout // (8 if i % 4 == 0 and not narrow else 4)
+    cout = 24 if narrow else 136
+    return (batch, 64, cout, 3, 1, levels[:2]), cout // (8 if i % 4 == 1 and not narrow else 4)
+
+
+for _hmax, _levels in HALO_GSTATS_LEVELS.items():
+    for _i, (_pick, _tile) in enumerate(HALO_PICK.items()):
+        if _hmax == 81 and _pick in HALO_FALLBACK_81:
+            continue                                                      # (their fallback is pick 3's tile)
+        _c, _g = _halo_gstats_case(_pick == 5, 2, _levels, _i)
+        _stat_row("halo", _tile + (_hmax, 1), "fwd_gstats", "bf16", {"conv.halo": _pick}, _c, why=TAIL if _i % 2 else MIXED, groups=_g)
+for _i, (_pick, _tile) in enumerate(HALO_TWIN_PICK.items()):
+    _c, _g = _halo_gstats_case(_pick == 15, 4, TINY_PYRAMID, _i)
+    _stat_row("halo", _tile + (33, 0), "fwd_gstats", "bf16", {"conv.halo": _pick}, _c, why=TAIL if _i % 2 else MIXED, groups=_g)
+
+# ---- ... resident-patch kernel: takes no group statistics (smallc_rule); the call goes to the register-staged kernel ------
+_stat_row("igemm", (64, 32, 4, 1), "fwd_gstats", "bf16", {"conv.smallc": 1}, (2, 8, 32, 3, 1, TINY_PYRAMID),
+          note="fallback: the resident-patch kernel takes no group statistics", why=MIXED, groups=8)
+# ---- a skipped level whose follow-up launch does not take the channel count (12 / 4 does not divide 256): refused up front
+_stat_row("igemm", (64, 16, 4, 1), "fwd_gstats", "bf16", PLAIN, (2, 24, 12, 3, 1, TINY_PYRAMID),
+          note="refused: stats_followup_ok", why=MIXED, groups=3)
+
+# ---- the fused-normalisation halo tiles (KD6D_CONV_HALO_NORM_TILES): GroupNorm and BatchNorm launches ----------------------
+# whole levels only; conv.halo = 3 sends these tiny maps to the halo kernel, the NORM tile follows the map width
+HALO_NORM = [((33, 0), {"conv.halo": 3}, [(8, 8), (4, 4)], "up to 32 wide"),
+             ((65, 1), {"conv.halo": 3}, [(2, 40), (1, 16)], "33 ... 63 wide"),
+             ((65, 1), {"conv.halo": 3}, [(1, 64)], "64 wide"),
+             ((65, 1), {"conv.halo": 3, "conv.halo_pairing": 0}, [(8, 8), (4, 4)], "up to 32 wide, no twins"),
+             ((81, 1), {"conv.halo": 3}, [(2, 72), (1, 16)], "65 ... 79 wide"),
+             ((81, 1), {"conv.halo": 3}, [(1, 80)], "80 wide")]
+for _hp, _o, _levels, _why in HALO_NORM:
+    for _norm, _g in (("group", 32), ("batch", 0)):
+        _stat_row("halo_norm", (128, 128, 4, 2) + _hp, "fwd_norm", "bf16", _o, (2, 128, 128, 3, 1, _levels), why=_why, norm=_norm,
+                  groups=_g)
+# ... and the register-staged kernel's, one launch of each kind per dtype
+for _dtype in ("bf16", "f32"):
+    for _norm, _g in (("group", 32), ("batch", 0)):
+        _stat_row("igemm", (64, 64, 2, 2), "fwd_norm", _dtype, {"conv.halo": 0}, (2, 8, 128, 3, 1, [(8, 8), (4, 4)]),
+                  norm=_norm, groups=_g)
+
+# ---- NORM = true and XF = true register-staged tiles: every tile in bf16 and fp32 -----------------------------------------
+# BatchNorm on load needs stride 1: the two stride-2 shapes of IGEMM_FWD are replaced
+IGEMM_XF = [(v, c) for v, c in IGEMM_FWD if c[4] == 1] + [((64, 32, 4, 1), (2, 8, 24, 3, 1, [(19, 17)])),
+                                                        ((128, 128, 2, 2), (1, 8, 200, 1, 1, [(157, 157)]))]
+for _dtype in ("bf16", "f32"):
+    for _v, _c in IGEMM_FWD:            # (the 128 x 64 tile has two rules: N <= 64, and N > 64 with too few tiles of 128 x 128)
+        _stat_row("igemm", _v, "fwd_block", _dtype, {}, _c, why="N <= 64" if _c[2] <= 64 else "N > 64", replicas=REPLICAS)
+    for _v, _c in IGEMM_XF:
+        _stat_row("igemm", _v, "fwd_xf", _dtype, {}, _c, why="N <= 64" if _c[2] <= 64 else "N > 64", replicas=REPLICAS)
+
+BY_ID = {r.id: r for r in ROWS + STAT_ROWS}
 TORCH_DTYPE = {"bf16": torch.bfloat16, "f32": torch.float32}
 
 
@@ -295,7 +420,9 @@ def epilogue_inputs(row):
     B, cin, cout, k, stride, levels = row.case
     g = torch.Generator().manual_seed(7 + cout)
     res = [round_to(torch.randn(B, cout, h, w, generator=g), TORCH_DTYPE[row.dtype]) for h, w in geometry(row.case)["levels_out"]]
-    return dict(res=res, scale=torch.rand(cout, generator=g) + 0.5, shift=torch.randn(cout, generator=g))
+    # (per-level factors that are powers of two: exact, so the tolerance of the epilogue call stays what it was)
+    seg = torch.tensor((2.0, 0.25, 4.0, 0.5, 8.0)[:len(levels)])
+    return dict(res=res, scale=torch.rand(cout, generator=g) + 0.5, shift=torch.randn(cout, generator=g), seg_scale=seg)
 
 
 # ---- references ----------------------------------------------------------------------------------------------------------
@@ -338,9 +465,10 @@ def random_reference(row):
 
 
 def epilogue_reference(conv, epi):
-    """scale, shift, leaky ReLU (0.1) and the residual behind the convolutions `conv` (test_conv_fwd_splitk's epilogue)."""
-    return [F.leaky_relu(c * epi["scale"].view(1, -1, 1, 1) + epi["shift"].view(1, -1, 1, 1), 0.1) + r
-            for c, r in zip(conv, epi["res"])]
+    """scale, shift, the level's factor, leaky ReLU (0.1) and the residual behind the convolutions `conv`, in the order of
+    test_conv_fwd_epilogue."""
+    return [F.leaky_relu((c * epi["scale"].view(1, -1, 1, 1) + epi["shift"].view(1, -1, 1, 1)) * float(epi["seg_scale"][li]), 0.1) + r
+            for li, (c, r) in enumerate(zip(conv, epi["res"]))]
 
 
 # ---- comparisons -----------------------------------------------------------------------------------------------------------
@@ -369,3 +497,138 @@ def check_random(got, ref, dtype, stored, what=""):
 def check_random_wgrad(got, ref, what=""):
     """Weight gradient of the random pass: 2e-4 relative to the largest reference entry (test_conv_wgrad)."""
     torch.testing.assert_close(got, ref, rtol=2e-4, atol=2e-4 * max(float(ref.abs().max()), 1.0), msg=lambda m: "%s: %s" % (what, m))
+
+
+# ======== fused statistics: plans, inputs, exact references and the word comparison ===================================
+def stat_flags(row):
+    """plan_conv flags of a STAT_ROWS row's launch."""
+    e = row.extra
+    return {"fwd_gstats": dict(stats=1, groups=e.get("groups", 0)),
+            "fwd_norm": dict(stats=1, groups=e.get("groups", 0), norm=1),
+            "fwd_block": dict(stats=1, replicas=e.get("replicas", 0)),
+            "fwd_xf": dict(stats=1, replicas=e.get("replicas", 0), xf=1)}[row.kind]
+
+
+def planned_stat(lib, row, ncu):
+    """(list, variant, plan) of a STAT_ROWS row's launch; a halo plan with the fused epilogue is of list halo_norm."""
+    p = P.plan_conv(lib, P.Layer(*row.case), "fwd", P.BF16 if row.dtype == "bf16" else P.F32, ncu=ncu, **stat_flags(row),
+                    **plan_options(row))
+    name = FWD_FAMILY[p.family]
+    tile = (p.BP, p.BC, p.WP, p.WC)
+    v = {"smallc": (p.CG, p.NB, 0, 0, 0, 0), "halo": tile + (p.HMAX, p.PDB), "glds": tile + (p.NSTAGE, 0), "igemm": tile + (0, 0)}[name]
+    if name == "halo" and p.NORM:
+        name = "halo_norm"
+    assert bool(p.NORM) == (row.kind in ("fwd_norm", "fwd_block")) and bool(p.XF) == (row.kind == "fwd_xf"), row.id
+    assert bool(p.fused_epilogue) == bool(p.NORM)
+    return name, v, p
+
+
+def fusable(lib, row):
+    """kd6d_conv2d_fwd_norm_fusable of a fwd_norm row, from the host build of the rule."""
+    kind = 1 if row.extra["norm"] == "group" else 2
+    return P.fusable(lib, P.Layer(*row.case), P.BF16 if row.dtype == "bf16" else P.F32, kind, row.extra["groups"], **plan_options(row))
+
+
+def level_rows(row):
+    """[(first GEMM row, pixels per image, summed by the epilogue)] of the destination levels, as set_stats sees them."""
+    out, m = [], 0
+    for h, w in geometry(row.case)["levels_out"]:
+        out.append((m, h * w, (h * w) % 16 == 0 and m % 16 == 0))
+        m += row.case[0] * h * w
+    return out
+
+
+def row_key(row, m):
+    """The (level, image) key of GEMM row m: level * batch + image.  THE layout of every group-statistics reference
+    here and of the accumulators kd6d_gn_relu_fwd consumes: level-major, image-major, then group, then {sum, sumsq}."""
+    key = 0
+    for li, (m0, hw, _) in enumerate(level_rows(row)):
+        if m >= m0:
+            key = li * row.case[0] + (m - m0) // hw
+    return key
+
+
+def row_keys(row):
+    """row_key of every GEMM row, as one int64 tensor."""
+    B = row.case[0]
+    return torch.cat([(li * B + torch.arange(B)).repeat_interleave(hw) for li, (m0, hw, _) in enumerate(level_rows(row))])
+
+
+@functools.lru_cache(maxsize=16)
+def _narrow_inputs(case_key):
+    B, cin, cout, k, stride, levels = case_key
+    g = torch.Generator().manual_seed(777 + 131 * cin + 17 * cout + k)
+    one = lambda *shape: torch.randint(-1, 2, shape, generator=g).float()
+    return dict(xs=[one(B, cin, h, w) for h, w in levels], w=one(cout, cin, k, k),
+                shift=torch.randint(-2, 3, (cout,), generator=g).float())
+
+
+def narrow_inputs(row):
+    """xs, w of {-1, 0, 1} and an integer shift of {-2 .. 2} per channel: the statistics passes.  With |y| <= 255 every fp32
+    partial sum of squares over the at most 256 rows of a tile is an integer below 2^24: exact in any order."""
+    return _narrow_inputs(_key(row.case))
+
+
+@functools.lru_cache(maxsize=16)
+def _narrow_reference(case_key):
+    B, cin, cout, k, stride, levels = case_key
+    inp = _narrow_inputs(case_key)
+    return [F.conv2d(x.double(), inp["w"].double(), inp["shift"].double(), stride=stride, padding=k // 2) for x in inp["xs"]]
+
+
+def narrow_reference(row):
+    """conv + shift of narrow_inputs in fp64, per level (B, cout, h, w): integers.  Do not modify the result."""
+    return _narrow_reference(_key(row.case))
+
+
+def packed_rows(ys):
+    """(M, cout) as the kernels pack the levels: level-major, image-major, then pixels."""
+    return torch.cat([y.permute(0, 2, 3, 1).reshape(-1, y.shape[1]) for y in ys])
+
+
+def channel_sums(rows):
+    """{sum[N], sumsq[N]} of an (M, N) tensor: Python integers for an integer tensor (exact), else fp64."""
+    t = rows.to(torch.int64) if torch.equal(rows, rows.round()) else rows.double()
+    return t.sum(0).tolist() + (t * t).sum(0).tolist()
+
+
+def group_sums(rows, row, groups, keys=None):
+    """{sum, sumsq} per (key, group) of an (M, N) tensor, in the layout of row_key; `keys`: the key of every GEMM row."""
+    B, cout = row.case[0], row.case[2]
+    nkeys = B * len(row.case[5])
+    if keys is None:
+        keys = row_keys(row)
+    t = rows.to(torch.int64) if torch.equal(rows, rows.round()) else rows.double()
+    t = t.reshape(rows.shape[0], groups, cout // groups)
+    s1 = torch.zeros(nkeys, groups, dtype=t.dtype).index_add_(0, keys, t.sum(2))
+    s2 = torch.zeros(nkeys, groups, dtype=t.dtype).index_add_(0, keys, (t * t).sum(2))
+    return torch.stack([s1, s2], dim=2).reshape(-1).tolist()
+
+
+def check_stat_words(words, want, what=""):
+    """Exact: accumulators as [lo, hi] int64 word pairs (kd6d_det.h, unit 2^-32) against integer sums: hi * 2^47 + lo ==
+    S * 2^32 in Python integers.  No rounding anywhere."""
+    assert len(words) == len(want), (what, len(words), len(want))
+    bad = [i for i, ((lo, hi), s) in enumerate(zip(words, want)) if (hi << 47) + lo != int(s) << 32]
+    if bad:
+        i = bad[0]
+        raise AssertionError("%s: %d of %d statistics differ from the exact sums; first at %d: got %r / 2^32, want %d" % (
+            what, len(bad), len(want), i, (words[i][1] << 47) + words[i][0], want[i]))
+
+
+def words_of(sums):
+    """The accumulator words an exact kernel leaves for integer sums (host tests)."""
+    out = []
+    for s in sums:
+        q = abs(int(s)) << 32
+        sign = -1 if s < 0 else 1
+        out.append([sign * (q & ((1 << 47) - 1)), sign * (q >> 47)])
+    return out
+
+
+def check_stat_values(words, want, what=""):
+    """Random pass: the accumulators' values against fp64 sums of the stored tensor at the project's statistics tolerance
+    (the kernel adds fp32 partial sums, rounded once each, so no word comparison here)."""
+    got = torch.tensor([hi * 2.0 ** 15 + lo * 2.0 ** -32 for lo, hi in words], dtype=torch.float64)
+    ref = torch.tensor(want, dtype=torch.float64)
+    torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-4 * max(float(ref.abs().max()), 1.0), msg=lambda m: "%s: %s" % (what, m))

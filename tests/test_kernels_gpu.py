@@ -1120,7 +1120,8 @@ FUSED_GN_CASES = [
     (16, 128, [(32, 32), (16, 16), (8, 8), (4, 4)], -1),         # ... at the benchmark batch (128x128 twin tiles)
     (16, 256, [(32, 32), (16, 16), (8, 8), (4, 4), (2, 2)], -1),  # teacher towers: two channel tiles, 2x2 level
     (3, 128, [(15, 20), (8, 10), (4, 5)], -1),                   # odd maps (full-frame levels)
-    (2, 256, [(60, 80), (30, 40), (15, 20), (8, 10), (4, 5)], -1),  # maps 80 wide: not the halo kernel
+    # maps 80 wide: the halo kernel's HMAX 81 tiles (conv.halo_wide = 1); 15 x 20 is no whole level: not fusable, two launches
+    (2, 256, [(60, 80), (30, 40), (15, 20), (8, 10), (4, 5)], -1),
     (3, 128, [(12, 12), (6, 6), (3, 3)], 0),                     # halo kernel off
 ]
 
