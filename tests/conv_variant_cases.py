@@ -23,6 +23,7 @@ word with the integer sums of the fp64 reference.  STAT_ROWS holds the rows of t
 instantiations (NORM, XF, the fused-normalisation halo tiles), compared the same way."""
 import collections
 import functools
+from fractions import Fraction
 
 import torch
 import torch.nn.functional as F
@@ -605,23 +606,31 @@ def group_sums(rows, row, groups, keys=None):
     return torch.stack([s1, s2], dim=2).reshape(-1).tolist()
 
 
-def check_stat_words(words, want, what=""):
-    """Exact: accumulators as [lo, hi] int64 word pairs (kd6d_det.h, unit 2^-32) against integer sums: hi * 2^47 + lo ==
-    S * 2^32 in Python integers.  No rounding anywhere."""
+def _scaled(s, unit):
+    """s * 2^unit without rounding: a Python integer for an integer sum, else a Fraction (half and quarter integers of
+    the backward sums; a float converts exactly)."""
+    return s << unit if isinstance(s, int) else Fraction(s) * (1 << unit)
+
+
+def check_stat_words(words, want, what="", unit=32):
+    """Exact: accumulators as [lo, hi] int64 word pairs (kd6d_det.h, lo in units of 2^-unit: 32 for the forward
+    statistics, 52 for the sums of the reverse sweep) against exact sums (Python integers, Fractions or floats that hold
+    the sum exactly): hi * 2^47 + lo == S * 2^unit in Python integers / Fractions.  No rounding anywhere."""
     assert len(words) == len(want), (what, len(words), len(want))
-    bad = [i for i, ((lo, hi), s) in enumerate(zip(words, want)) if (hi << 47) + lo != int(s) << 32]
+    bad = [i for i, ((lo, hi), s) in enumerate(zip(words, want)) if (hi << 47) + lo != _scaled(s, unit)]
     if bad:
         i = bad[0]
-        raise AssertionError("%s: %d of %d statistics differ from the exact sums; first at %d: got %r / 2^32, want %d" % (
-            what, len(bad), len(want), i, (words[i][1] << 47) + words[i][0], want[i]))
+        raise AssertionError("%s: %d of %d statistics differ from the exact sums; first at %d: got %r / 2^%d, want %s" % (
+            what, len(bad), len(want), i, (words[i][1] << 47) + words[i][0], unit, want[i]))
 
 
-def words_of(sums):
-    """The accumulator words an exact kernel leaves for integer sums (host tests)."""
+def words_of(sums, unit=32):
+    """The accumulator words an exact kernel leaves for exact sums (host tests; kd6d_gn_relu_fwd's STATS_READY input)."""
     out = []
     for s in sums:
-        q = abs(int(s)) << 32
-        sign = -1 if s < 0 else 1
+        q = _scaled(s, unit)
+        assert q == int(q), "%r is no multiple of 2^-%d" % (s, unit)
+        q, sign = abs(int(q)), -1 if s < 0 else 1
         out.append([sign * (q & ((1 << 47) - 1)), sign * (q >> 47)])
     return out
 

@@ -816,9 +816,12 @@ def test_pool_upsample_eltwise(gpu_device, dtype):
     ops.eltwise(ops.ELT_RELU, xp, None, r)
     rb = torch.empty_like(xp)
     ops.eltwise(ops.ELT_RELU_BWD, xp, out, rb)
+    ad = torch.empty_like(xp)
+    ops.eltwise(ops.ELT_ADD, xp, out, ad)
     torch.cuda.synchronize()
     assert torch.equal(r.cpu().float(), F.relu(xp.cpu().float()))
     assert torch.equal(rb.cpu().float(), torch.where(xp.cpu().float() > 0, out.cpu().float(), torch.zeros(())))
+    assert torch.equal(ad.cpu().float(), round_to(xp.cpu().float() + out.cpu().float(), dtype))      # one rounding of the fp32 sum
     img = torch.randn(2, 3, 5, 7, generator=g)
     nh = ops.image_to_nhwc(img.to(dev), dtype)
     torch.cuda.synchronize()

@@ -2,32 +2,18 @@
 decisions of the BN / GN backwards, the GN backward workspace -- built for the host with g++ from the SAME header the
 launchers include (csrc/norm_plan.h through tests/norm_plan_host.cpp)."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import norm_plan_lib
+
 LL = ctypes.c_longlong
 DTYPES = [("bf16", 8), ("f32", 4)]
 
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("norm_plan") / "libnormplan.so")
-    subprocess.check_call(["g++", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so, os.path.join(HERE, "norm_plan_host.cpp")])
-    L = ctypes.CDLL(so)
-    for n in ("np_flush_lds_bytes", "np_bn_apply_lds_bytes", "np_bn_onepass_lds_bytes", "np_gn_bwd_lds_bytes"):
-        getattr(L, n).restype = LL
-    for n in ("np_grid_for", "np_bn_bwd_reduce_grid", "np_bn_pool_bwd_reduce_grid"):
-        getattr(L, n).argtypes = [LL]
-    L.np_colstats_grid.argtypes = [LL, ctypes.c_int]
-    L.np_bn_onepass_plan.argtypes = [LL, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, LL, ctypes.POINTER(ctypes.c_int)]
-    c = (ctypes.c_int * 9)()
-    L.np_constants(c)
-    L.k = dict(zip(("threads", "flush_lds", "bn_hold", "pool_hold", "gn_hold", "bn_blocks", "colstats_cap", "bn_reduce_cap",
-                    "gn_bwd_max_c"), c))
-    return L
+    return norm_plan_lib.build_lib(tmp_path_factory.mktemp("norm_plan"))
 
 
 def _bn_plan(L, items, pooled=0, resident=768, counter=1, enabled=1, max_granules=1 << 40):
